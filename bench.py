@@ -1,7 +1,15 @@
 """Headline benchmark: frames/sec of one G+D forward+backward training step (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the JSON line with the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step, ...).  `--dump-outputs DIR` then also writes what the last timed step handed its caller
+as DIR/<name>.npy (float32): the discriminator and generator losses and the generated frame (dump_outputs).  Inputs and initial
+weights are seeded, and the last timed step starts from the initial weights and optimiser state (written back outside the timed
+window), so two runs or two builds can be compared file by file.
+`--full` adds the measurements below, each of which costs runs of its own (`--no-roofline`, `--no-cpu-baseline`,
+`--no-extras` leave single ones out again).
 
 Workload (config.workload): BASELINE.json configs[2] - fewshot_pose 512x512, per-GPU batch 2, --adaptive_spade
 --warp_ref --spade_combine --remove_face_labels --no_flow_gt --no_vgg_loss (SURVEY.md section 8d "C3"), synthetic
@@ -9,7 +17,7 @@ labels/images, random-init weights.  One step = the body of the reference's trai
 no-grad G forward), D backward, Adam(D), G forward, D forward, full backward, Adam(G).  fp32 throughout (exact-fp32
 MFMA).  Weak scaling: the per-GPU batch is fixed, gradients are all-reduced over RCCL (flat.py).
 
-Besides the contract fields the JSON line carries
+With `--full` the JSON line also carries
   roofline     - the dominant kernel (the fp32 MFMA implicit-GEMM convolution) priced against the 157.3 TFLOP/s
                  fp32 matrix peak: algorithmic FLOPs per launch / average launch duration, measured with HIP events
                  on the launch stream around every launch of that kernel in an instrumented eager pass of the step
@@ -102,6 +110,57 @@ def make_data(batch, size, seed, device, opt=None):
     tl, ti, rl, ri = _synth().synth_pose_inputs(batch, size, size, seed) if opt is None else synth_inputs(opt, batch, seed)
     tl, ti, rl, ri = [t.to(device) for t in (tl, ti, rl, ri)]
     return [tl, ti, [None, None], [None, None], rl, ri, None, None, None]
+
+
+DUMP_MAX_ELEMENTS = 1 << 21     # per file (8 MB of float32): larger outputs are dumped as a fixed, seeded sample
+
+
+def dump_outputs(out_dir, outs):
+    """--dump-outputs: the last timed step's results as float32 .npy files.  `outs`: name -> tensor or list of scalar tensors
+    (losses).  The updated weights are not dumped: the first Adam step from the restored state moves parameters whose gradient is
+    zero up to rounding (biases in front of a normalisation) by up to the learning rate, in a direction set by that rounding.
+    An array above DUMP_MAX_ELEMENTS is replaced by the elements at sorted indices drawn from a generator seeded with 0, the same
+    indices on every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, v in outs.items():
+        if isinstance(v, (list, tuple)):
+            arrays[name] = torch.stack([x.float().reshape(()) for x in v])
+        else:
+            arrays[name] = v.float()
+    for name, t in arrays.items():
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            name += '_sample'
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMENTS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
+
+
+def step_state(model, opt_G, opt_D):
+    """name -> live tensor of everything a training step reads and rewrites for the next one: the networks' parameters and
+    buffers (spectral-norm vectors, running statistics) and the optimisers' moments, step counters and loss scales"""
+    d = dict(model.state_dict())
+    for tag, o in (('optimizer_G', opt_G), ('optimizer_D', opt_D)):
+        d.update({'%s.%s' % (tag, k): v for k, v in o.state_dict().items()})
+    return d
+
+
+def restore_step_state(saved, model, opt_G, opt_D):
+    """write the values of `saved` (step_state clones) back in place - the addresses a captured graph reads - and re-derive
+    the optimisers' cached weight layouts from them (flat.FlatAdam.refresh_layouts)"""
+    with torch.no_grad():
+        for k, t in step_state(model, opt_G, opt_D).items():
+            t.copy_(saved[k])
+    opt_G.refresh_layouts()
+    opt_D.refresh_layouts()
+
+
+def host_threads():
+    """CPU threads of the CPU baseline: OMP_NUM_THREADS where the launcher sets it, else the cores this process may run on
+    (os.cpu_count() counts the whole host, also where a share of it is granted), at most 64"""
+    n = int(os.environ.get('OMP_NUM_THREADS') or 0) or len(os.sched_getaffinity(0))
+    return max(1, min(n, 64))
 
 
 def cpu_baseline(size, batch, threads, use_reference=False):
@@ -276,7 +335,7 @@ def extras(device, size, steps=5):
     try:
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), '--workload', 'street', '--amp', 'O1', '--steps', '10', '--warmup', '3',
-               '--no-cpu-baseline', '--no-extras']
+               '--full', '--no-cpu-baseline', '--no-extras']
         pr = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         lines = [ln for ln in pr.stdout.splitlines() if ln.startswith('{')]
         if pr.returncode != 0 or not lines:
@@ -330,7 +389,14 @@ def main():
                     "loss scale, bf16x3 = split-bf16 operands; O0 (default, the headline) = exact fp32")
     ap.add_argument('--ngf', type=int, default=32, help='network width (32 = the reference default = the headline; smaller '
                     'values only for the emulated launcher test)')
+    ap.add_argument('--full', action='store_true', help='also measure the roofline, the CPU baseline and the extras (module '
+                    'docstring); a plain run times the steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the last timed step\'s outputs as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not args.full:
+        args.no_roofline = args.no_cpu_baseline = args.no_extras = True
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and not args.cpu_baseline_only:
         raise SystemExit(spawn_ranks(args.gpus))
     global WITH_VGG, WITH_FACE_D, AMP, WORKLOAD
@@ -347,7 +413,7 @@ def main():
         raise SystemExit("--face-d belongs to the pose workload")
 
     if args.cpu_baseline_only:
-        print(json.dumps(cpu_baseline(args.size, args.batch, min(os.cpu_count() or 1, 64), args.use_reference)), flush=True)
+        print(json.dumps(cpu_baseline(args.size, args.batch, host_threads(), args.use_reference)), flush=True)
         return
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -412,16 +478,30 @@ def main():
                                       overlap=not seg, split_backward=(_PIECES if (seg or (not g_only and os.environ.get('FSV_BENCH_SPLIT', '1') == '1')) else False))
     opt_G, opt_D = build_optimizers(segmented)
     data = make_data(args.batch, args.size, 1234 + rank, device, opt)
+    # --dump-outputs: the state before the first step, written back in front of the last timed step (outside the timed window).
+    # Every step trains on the last one's weights, and the float atomics of the split-K convolutions, the warp backward and the
+    # statistics make last-bit differences between runs that Adam and the GAN game grow from step to step (after 25 steps of the
+    # headline workload: losses apart by order 1).  From the initial state, the dumped step's outputs differ by one step's rounding.
+    initial_state = ({k: t.detach().clone() for k, t in step_state(model, opt_G, opt_D).items()}
+                     if args.dump_outputs else None)
 
     # one GPU: the generator-mode forward pass starts on a side stream next to the discriminator step (model.early_generator;
     # FSV_EARLY_G=0: the sequential order, in-box A/B).  With a process group the exchange sits between the two steps.
     model.early_generator = (not distributed) and os.environ.get('FSV_EARLY_G', '1') == '1'
 
+    # the outputs of the latest step (in graph mode: the capture's tensors, which every replay rewrites) for --dump-outputs;
+    # detached, so that no step's autograd graph outlives it (a live graph of the eager warm-up would reach into the capture)
+    last = {}
+
+    def keep(**outs):
+        last.update({k: [t.detach() for t in v] if isinstance(v, (list, tuple)) else v.detach() for k, v in outs.items()})
+
     def step():
         d_losses = model(data, mode='discriminator')
         M.loss_backward(opt, d_losses, opt_D, 1)
-        g_losses, _, _ = model(data, mode='generator')
+        g_losses, _, prev = model(data, mode='generator')
         M.loss_backward(opt, g_losses, opt_G, 0)
+        keep(d_losses=d_losses, g_losses=g_losses, fake=prev[2][:, -1])
 
     if g_only:
         # BASELINE configs[1]: "G-only fwd/bwd": the generator called directly, the mean of its image as the scalar, Adam(G) included
@@ -431,7 +511,9 @@ def main():
         def step():              # noqa: F811
             with conv_mod.stats_pass(device):
                 img = model.netG(label, ref_label, ref_img, [None, None])[0]
-            M.loss_backward(opt, [img.mean().view(1, 1)], opt_G, 0)
+            g_losses = [img.mean().view(1, 1)]
+            M.loss_backward(opt, g_losses, opt_G, 0)
+            keep(g_losses=g_losses, fake=img)
 
     use_graph = not args.no_graph
     mode = 'eager'
@@ -456,7 +538,8 @@ def main():
                 raise RuntimeError("injected GraphedIteration construction failure")
 
             def run():               # noqa: F811
-                gi(data)
+                d_losses, g_losses, _, prev = gi(data)
+                keep(d_losses=d_losses, g_losses=g_losses, fake=prev[2][:, -1])
             for _ in range(n_eager_warm + 1):          # eager warm-up calls, then the capture (followed by its first replay)
                 run()
             n_eager_warm += 1
@@ -480,7 +563,9 @@ def main():
         n_eager_warm = 0
         mode = 'emulated kernels on host tensors + gloo (CPU test infrastructure, not a measurement)'
     else:
-        n_eager_warm = max(1, min(args.warmup, 2)) if use_graph else args.warmup
+        # two eager steps before the capture whatever --warmup says: after one, the capture fails (unjoined side-stream work) and
+        # the eager fallback then stops at the dense-gradient set the aborted capture left behind
+        n_eager_warm = 2 if use_graph else args.warmup
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -513,18 +598,27 @@ def main():
     if world > 1 or force_dist:
         dist.barrier()
     sync()
+    paused = 0.0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if initial_state is not None and i == args.steps - 1:
+            sync()
+            r0 = time.perf_counter()
+            restore_step_state(initial_state, model, opt_G, opt_D)
+            sync()
+            paused += time.perf_counter() - r0
         run()
     sync()
     if world > 1:
         dist.barrier()
     sync()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - paused
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:          # before the --full passes below run the step again
+        dump_outputs(args.dump_outputs, last)
 
     frames = args.batch * world * args.steps
     hh, ww = int(opt.fineSize / opt.aspect_ratio), opt.fineSize
@@ -697,7 +791,7 @@ def main():
             rf['frac_in_timed_schedule'] = None if not its else its['frac']
             rf['avg_launch_us_in_timed_schedule'] = None if not its else its['avg_launch_us']
         if world == 1 and not args.no_cpu_baseline and not g_only:
-            result['cpu_baseline'] = cpu_baseline(args.size, args.batch, min(os.cpu_count() or 1, 64))
+            result['cpu_baseline'] = cpu_baseline(args.size, args.batch, host_threads())
         if world == 1 and not args.no_extras and not (WITH_VGG or WITH_FACE_D) and AMP == 'O0' and WORKLOAD == 'pose':
             result['extras'] = extras(device, args.size)
     if world > 1 or force_dist:

@@ -14,7 +14,7 @@ if [ -n "$SEL" ]; then
   grep -h "amp step vs\|FAILED\|Error" "$OUT/pytest.log" | head -20 | tee -a "$OUT/summary.txt"
 fi
 t0=$SECONDS
-timeout 900 python bench.py "$@" > "$OUT/bench.log" 2> "$OUT/bench.err"
+timeout 900 python bench.py --full "$@" > "$OUT/bench.log" 2> "$OUT/bench.err"
 echo "bench.py $*: exit $? in $((SECONDS-t0))s" | tee -a "$OUT/summary.txt"
 tail -n 1 "$OUT/bench.log" > "$OUT/bench.json"
 python - "$OUT/bench.json" <<'PY' | tee -a "$OUT/summary.txt"

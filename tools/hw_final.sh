@@ -13,7 +13,7 @@ t0=$SECONDS
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE_OK')" > "$OUT/smoke.log" 2>&1
 echo "smoke: exit $? in $((SECONDS-t0))s: $(tail -n 1 "$OUT/smoke.log")" | tee -a "$OUT/summary.txt"
 t0=$SECONDS
-timeout 600 python bench.py > "$OUT/bench_default.log" 2>&1
+timeout 600 python bench.py --full > "$OUT/bench_default.log" 2>&1
 echo "bench.py: exit $? in $((SECONDS-t0))s" | tee -a "$OUT/summary.txt"
 tail -n 1 "$OUT/bench_default.log" | cut -c1-400 | tee -a "$OUT/summary.txt"
 bash tools/hw_prof.sh "${1:-final}_prof" > /dev/null 2>&1

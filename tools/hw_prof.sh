@@ -17,7 +17,7 @@ run() {
 # WARGS: workload selection of every bench command (e.g. WARGS="--workload street --amp O1"; default: the headline pose fp32 step)
 WARGS=${WARGS:-}
 cd "$ROOT"
-run bench_full   600 python bench.py $WARGS --steps 20 --warmup 5 --no-cpu-baseline --no-extras
+run bench_full   600 python bench.py $WARGS --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras
 cd /tmp
 BARGS="$WARGS --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-roofline"
 run prof         300 rocprofv3 --kernel-trace --stats --output-format csv -d "$RAW/prof" -o p -- python "$ROOT/bench.py" $BARGS

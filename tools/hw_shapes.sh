@@ -12,6 +12,6 @@ timeout 300 python tools/shape_profile.py --workload street --amp O1 --top 80 --
 echo "street shapes: exit $?" | tee -a "$OUT/summary.txt"
 timeout 300 python tools/aten_census.py > "$OUT/aten_census.txt" 2>&1
 echo "census: exit $?" | tee -a "$OUT/summary.txt"
-timeout 400 python bench.py --no-cpu-baseline > "$OUT/bench_default.log" 2>&1
+timeout 400 python bench.py --full --no-cpu-baseline > "$OUT/bench_default.log" 2>&1
 echo "bench: exit $?" | tee -a "$OUT/summary.txt"
 tail -n 1 "$OUT/bench_default.log" | cut -c1-600 | tee -a "$OUT/summary.txt"
