@@ -8,6 +8,7 @@ warp goes through the gfx950 kernels, activations stay channels-last between lay
 of the reference are folded into kernel epilogues (bias+LeakyReLU, tanh, sigmoid, flow scale, residual add,
 BN+LeakyReLU, SPADE denorm+modulate+LeakyReLU).
 """
+import contextlib
 import math
 import weakref
 
@@ -173,19 +174,20 @@ class SPADEConv2d(nn.Module):
 
 
 class SPADE(nn.Module):
-    """Reference normalization.py:18-52 with ks = 1: param-free BatchNorm + sequential (1+gamma)*x+beta per map."""
+    """Reference normalization.py:18-52 (ks = 1 or 3): param-free BatchNorm + sequential (1+gamma)*x+beta per map."""
 
-    def __init__(self, norm_nc, hidden_nc, params_free=False):
+    def __init__(self, norm_nc, hidden_nc, params_free=False, ks=1):
         super().__init__()
         if not isinstance(hidden_nc, list):
             hidden_nc = [hidden_nc]
         self.n_hidden = len(hidden_nc)
         self.params_free = params_free
+        self.ks = ks
         for i, nh in enumerate(hidden_nc):
             if not params_free or i != 0:
                 s = str(i + 1) if i > 0 else ''
-                setattr(self, 'mlp_gamma%s' % s, Conv2d(nh, norm_nc, 1))
-                setattr(self, 'mlp_beta%s' % s, Conv2d(nh, norm_nc, 1))
+                setattr(self, 'mlp_gamma%s' % s, Conv2d(nh, norm_nc, ks, padding=ks // 2))
+                setattr(self, 'mlp_beta%s' % s, Conv2d(nh, norm_nc, ks, padding=ks // 2))
         self.norm = BatchNorm(norm_nc, affine=False)
         self.norm_nc = norm_nc
 
@@ -218,8 +220,9 @@ class SPADE(nn.Module):
 class SPADEResnetBlock(nn.Module):
     """Reference architecture.py:71-108 (conv_params_free=False; SPADE or plain-BatchNorm flavour)."""
 
-    def __init__(self, fin, fout, hidden_nc=0, spade=True, norm_params_free=False):
+    def __init__(self, fin, fout, hidden_nc=0, spade=True, norm_params_free=False, spade_ks=1):
         super().__init__()
+        self.spade_ks = spade_ks
         fhidden = min(fin, fout)
         self.learned_shortcut = fin != fout
         self.spade = spade
@@ -228,10 +231,10 @@ class SPADEResnetBlock(nn.Module):
         if self.learned_shortcut:
             self.conv_s = Conv2d(fin, fout, 1, bias=False, spectral=True)
         if spade:
-            self.bn_0 = SPADE(fin, hidden_nc, norm_params_free)
-            self.bn_1 = SPADE(fhidden, hidden_nc, norm_params_free)
+            self.bn_0 = SPADE(fin, hidden_nc, norm_params_free, spade_ks)
+            self.bn_1 = SPADE(fhidden, hidden_nc, norm_params_free, spade_ks)
             if self.learned_shortcut:
-                self.bn_s = SPADE(fin, hidden_nc, norm_params_free)
+                self.bn_s = SPADE(fin, hidden_nc, norm_params_free, spade_ks)
         else:
             self.bn_0 = BatchNorm(fin)
             self.bn_1 = BatchNorm(fhidden)
@@ -247,17 +250,20 @@ class SPADEResnetBlock(nn.Module):
         if up and not fold:
             x = ops.upsample2x(x)
         if self.spade:
-            conv3 = ops.spade_conv3_enabled() and not ops.spade_pair_enabled()      # (two opt-ins that both want bn_0: the pair wins)
+            # the fused SPADE launches (two-site, bn_s -> conv_s, actvn(bn) -> conv3x3) are 1x1-only: a 3x3 SPADE (--spade_ks 3) declines
+            # them here and runs as its own launch (csrc/spade_k3.hip) followed by the gather-GEMM convolution
+            k1 = self.spade_ks == 1
+            conv3 = k1 and ops.spade_conv3_enabled() and not ops.spade_pair_enabled()      # (two opt-ins that both want bn_0: the pair wins)
             if self.learned_shortcut:
                 # bn_s and bn_0 normalise the same x with the same maps: one two-site launch (ops.spade_pair)
-                if ops.spade_pair_enabled():
+                if k1 and ops.spade_pair_enabled():
                     with ops.spade_pair():
                         hs = self.bn_s(x, label, nw[2], act=ACT_NONE, up=fold)
                         h0 = self.bn_0(x, label, nw[0], act=ACT_LRELU, up=fold)
                     x_s = self.conv_s(hs)
                 else:
                     # bn_s -> conv_s as ONE kernel where csrc/spade_conv.hip covers the widths (ops.spade_into_conv)
-                    with ops.spade_into_conv():
+                    with (ops.spade_into_conv() if k1 else contextlib.nullcontext()):
                         x_s = self.conv_s(self.bn_s(x, label, nw[2], act=ACT_NONE, up=fold))
                     h0 = None if conv3 else self.bn_0(x, label, nw[0], act=ACT_LRELU, up=fold)
             else:
@@ -310,6 +316,7 @@ class LabelEmbedder(nn.Module):
         self.unet = 'unet' in netS
         self.decode = 'decoder' in netS or self.unet
         self.n = n = opt.n_downsample_G
+        self.embed_ks = getattr(opt, 'embed_ks', 1)
         self.params_free_layers = params_free_layers if params_free_layers != -1 else n
         ch = _channels(nf, n + 1)
         self.conv_first = _seq(Conv2d(input_nc, nf, 3, padding=1), _Slot())
@@ -354,9 +361,12 @@ class LabelEmbedder(nn.Module):
             cur = ops.cat_channels([cur, skips[i + 1]])
         if i >= self.params_free_layers:
             return getattr(self, 'up_%d' % i)[1](cur, act=ACT_LRELU, up=True)      # generator.py:559-563: Upsample -> conv3x3
+        w, b = weights[i]
+        if self.embed_ks != 1:
+            # --embed_ks 3 (generator.py:566-568): nearest x2 up-sampling, then the per-sample 3x3 convolution (padding 1), LeakyReLU
+            return ops.batch_conv(ops.upsample2x(cur), w, b, act=ACT_LRELU)
         # a 1x1 convolution commutes with nearest up-sampling: run the generated-weight conv on the quarter-size
         # tensor, then up-sample (bit-identical, 4x fewer MACs and bytes)
-        w, b = weights[i]
         return ops.upsample2x(ops.batch_conv(cur, w, b, act=ACT_LRELU))
 
     def decode_maps(self, state, weights=None):
@@ -431,8 +441,16 @@ class FewShotGenerator(nn.Module):
         self.n_downsample_A = getattr(opt, 'n_downsample_A', 2)
         if getattr(opt, 'use_label_ref', 'mul') != 'mul' or getattr(opt, 'res_for_ref', False):
             raise NotImplementedError("only use_label_ref='mul' with SPADEConv2d encoders is on the hot path")
-        if opt.spade_ks != 1 or opt.embed_ks != 1 or opt.conv_ks != 3:
-            raise NotImplementedError("spade_ks = embed_ks = 1, conv_ks = 3 (the defaults of every shipped script)")
+        if opt.conv_ks != 3:
+            raise NotImplementedError("conv_ks = %r: only 3 (the reference hard-codes padding 1 and a 3x3 get_conv_weights)"
+                                      % (opt.conv_ks,))
+        if opt.spade_ks not in (1, 3):
+            raise NotImplementedError("spade_ks = %r: only 1 and 3" % (opt.spade_ks,))
+        if opt.embed_ks not in (1, 3):
+            raise NotImplementedError("embed_ks = %r: only 1 and 3" % (opt.embed_ks,))
+        if opt.spade_ks != 1 and str(getattr(opt, 'amp', '') or '').lower() not in ('', 'o0', 'fp32', 'f32'):
+            raise NotImplementedError("spade_ks = 3 under --amp (the 3x3 SPADE kernel is exact fp32 only)")
+        self.spade_ks, self.embed_ks = opt.spade_ks, opt.embed_ks
         self.n_downsample_G = n = opt.n_downsample_G
         nf = opt.ngf
         nf_max = min(1024, nf * (2 ** n))
@@ -461,10 +479,11 @@ class FewShotGenerator(nn.Module):
                 ch_in, ch_out = ch[i], ch[i + 1]
                 ch_h = ch_hidden[i][0]
                 names = ['fc_spade_0', 'fc_spade_1', 'fc_spade_s']
-                outs = [(ch_h + 1) * 2, (ch_h + 1) * (1 if ch_in != ch_out else 2), (ch_h + 1) * 2]
+                sk2, ek2 = self.spade_ks ** 2, self.embed_ks ** 2          # generator.py:83-95
+                outs = [(ch_h * sk2 + 1) * 2, (ch_h * sk2 + 1) * (1 if ch_in != ch_out else 2), (ch_h * sk2 + 1) * 2]
                 if self.adap_embed:
                     names.append('fc_spade_e')
-                    outs.append(ch_in + 1)
+                    outs.append(ch_in * ek2 + 1)
                 for name, fo in zip(names, outs):
                     layers = [Linear(ch_out, ch_out), _Slot()]
                     for _ in range(1, self.n_fc_layers):
@@ -475,7 +494,8 @@ class FewShotGenerator(nn.Module):
                                              params_free_layers=(self.n_adaptive_layers if self.adap_embed else 0))
         for i in reversed(range(n + 1)):
             setattr(self, 'up_%d' % i, SPADEResnetBlock(ch[i + 1], ch[i], hidden_nc=ch_hidden[i], spade=True,
-                                                       norm_params_free=(self.adap_spade and i < self.n_adaptive_layers)))
+                                                       norm_params_free=(self.adap_spade and i < self.n_adaptive_layers),
+                                                       spade_ks=self.spade_ks))
         self.conv_img = Conv2d(nf, 3, 3, padding=1)
         if self.n_shot > 1:                # generator.py:128-134: key / query encoders of the attention module
             self.atn_query_first = SPADEConv2d(input_nc, nf)
@@ -532,15 +552,15 @@ class FewShotGenerator(nn.Module):
         return layers[last](x)
 
     @staticmethod
-    def _pairs(f, npairs, cout, cin):
-        """f [b, L] -> npairs x [weight [b, cout, cin, 1, 1], bias [b, cout]] read off the front of each row
+    def _pairs(f, npairs, cout, cin, k=1):
+        """f [b, L] -> npairs x [weight [b, cout, cin, k, k], bias [b, cout]] read off the front of each row
         (generator.py reshape_weight slices the flattened FC output the same way).  One split instead of nested slicing:
         its backward is ONE concatenation (ops.split_cols) instead of a zero-fill + copy + add per slice."""
-        sizes = [cout * cin, cout] * npairs
+        sizes = [cout * cin * k * k, cout] * npairs
         rest = f.shape[1] - sum(sizes)
         parts = ops.split_cols(f, sizes + ([rest] if rest > 0 else []))
         b = f.shape[0]
-        return [[parts[2 * k].reshape(b, cout, cin, 1, 1), parts[2 * k + 1]] for k in range(npairs)]
+        return [[parts[2 * j].reshape(b, cout, cin, k, k), parts[2 * j + 1]] for j in range(npairs)]
 
     _MLP_NAMES = ('fc_spade_e', 'fc_spade_0', 'fc_spade_1', 'fc_spade_s')
 
@@ -574,11 +594,11 @@ class FewShotGenerator(nn.Module):
         if self.adap_embed:
             fe = mlp('fc_spade_e').view(b, -1)
             # the reference drops the trailing ch_in entries, then reads weight | bias off what is left: the same split
-            embedding_weights = self._pairs(fe, 1, ch_in, ch_out)[0]
+            embedding_weights = self._pairs(fe, 1, ch_in, ch_out, self.embed_ks)[0]
 
         def two(name, co):
             f = mlp(name).view(b, -1)
-            return self._pairs(f, 2, co, ch_h)
+            return self._pairs(f, 2, co, ch_h, self.spade_ks)
         return embedding_weights, [two('fc_spade_0', ch_out), two('fc_spade_1', ch_in), two('fc_spade_s', ch_out)]
 
     def attention_encode(self, img, name):

@@ -55,6 +55,9 @@ lib.register_sigs({
     "fsv_spade_bwd_elem": [c_p, c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_p, c_i, c_i, c_i, c_ll, c_i, c_i, c_i, c_p],
     "fsv_spade_mod_bwd": [c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp, c_pp, c_p,
                           c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_i, c_p],
+    # x mean rstd h | nmaps maps wt bcat ch w_bstride b_bstride gb | N H W C ldw stat_bstride act up stream
+    "fsv_spade_k3_fwd": [c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp, c_pp,
+                         c_i, c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_p],
     "fsv_spade_conv_s_supported": [c_i, c_i, c_i],
     "fsv_spade_conv_s_fwd": [c_p, c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp,
                              c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_p, c_i, c_i, c_p, c_p],
@@ -1398,7 +1401,8 @@ def _streams_mod():
 class _SpadeFn(torch.autograd.Function):
     """h = act(spade(x; maps, weights)).  Argument list: x, run_mean, run_var, then per map (map, wg, wb, bg, bb).
 
-    wg/wb are OIHW 1x1 weights: [C, Ch, 1, 1] (fixed) or [B, C, Ch, 1, 1] (generated per sample).
+    wg/wb are OIHW weights: [C, Ch, k, k] (fixed) or [B, C, Ch, k, k] (generated per sample), k = 1 or 3 (--spade_ks 3:
+    _forward_k3 / _backward_k3).
     """
 
     @staticmethod
@@ -1435,6 +1439,8 @@ class _SpadeFn(torch.autograd.Function):
         chs = [m.shape[1] for m in maps]
         ctx.up = up
         lib.check_device(x, *maps)
+        if nmaps and wgs[0].shape[-1] != 1:
+            return _SpadeFn._forward_k3(ctx, act, up, training, run_mean, x, mean, rstd, maps, wgs, wbs, bgs, bbs, n, c, h, w)
         # fast path (every production width): ONE preparation launch per map builds the combined [gamma | beta] operands
         # that the modulation kernel, the backward recompute and the data gradient all use as they are
         ctx.fast = (c % 16 == 0) and _os.environ.get('FSV_SPADE_FAST', '1') == '1'
@@ -1581,7 +1587,110 @@ class _SpadeFn(torch.autograd.Function):
         return hout
 
     @staticmethod
+    def _forward_k3(ctx, act, up, training, run_mean, x, mean, rstd, maps, wgs, wbs, bgs, bbs, n, c, h, w):
+        """--spade_ks 3 (normalization.py:18-52 with ks = 3): ONE launch of csrc/spade_k3.hip (the 3x3 gamma / beta GEMMs on the fp32
+        matrix cores, the modulation of every map and the activation in its epilogue).  The 1x1-only fusions decline it on purpose:
+        no site is handed to spade_into_conv (bn_s -> conv_s, FSV_SPADE_CONV3) or spade_pair (FSV_SPADE_PAIR), there is no f16 form
+        (networks.FewShotGenerator refuses --amp with spade_ks 3), and the operands are prepared on every call (no
+        FSV_SPADE_PREP_CACHE entry that a replayed graph could leave stale).  A forward that keeps a graph also writes gamma | beta
+        ([P][2C] per map): the backward runs the element-wise chain fsv_spade_bwd_elem on it instead of recomputing the 9 * Ch-deep
+        GEMMs (profiles/spade_k3_notes.md)."""
+        nmaps = len(maps)
+        chs = [m.shape[1] for m in maps]
+        for k in range(nmaps):
+            if tuple(wgs[k].shape[-2:]) != (3, 3) or tuple(wbs[k].shape[-2:]) != (3, 3):
+                raise NotImplementedError("SPADE weights of shape %s: 1x1 or 3x3 only" % (tuple(wgs[k].shape),))
+        if c % 4 or any(ch % 4 for ch in chs) or x.dtype != torch.float32 or any(m.dtype != torch.float32 for m in maps):
+            raise NotImplementedError("3x3 SPADE: fp32 tensors, channels a multiple of 4 (C %d, maps %s)" % (c, chs))
+        g3 = Geom(3, 3, 1, 1)
+        ldw = (2 * c + 31) // 32 * 32
+        wts, bcats, wcats, wstr, bstr = [], [], [], [], []
+        for k in range(nmaps):
+            per_sample = wgs[k].dim() == 5
+            wcat = torch.cat([wgs[k].detach(), wbs[k].detach()], dim=-4)               # [(B,) 2C, Ch, 3, 3]: gamma | beta as one conv
+            bcat = torch.cat([bgs[k].detach(), bbs[k].detach()], dim=-1).contiguous()
+            wt, kpad, ldw_k = prep_weight(wcat, 0, g3)
+            assert ldw_k == ldw
+            wts.append(wt); bcats.append(bcat); wcats.append(wcat)
+            wstr.append(kpad * ldw if per_sample else 0)
+            bstr.append(2 * c if per_sample else 0)
+        keep = _keeps_graph(ctx)
+        gbs = [empty_nhwc(n, 2 * c, h, w, x) for _ in range(nmaps)] if keep else []
+        hout = empty_nhwc(n, c, h, w, x)
+        with profile.scope('fsv_spade_k3_kernel' + (' P%d C%d K%s' % (n * h * w, c, '+'.join(map(str, chs))) if profile.detail() else ''),
+                           2.0 * n * h * w * 2 * c * 9 * sum(chs)):
+            lib.call("fsv_spade_k3_fwd", lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(hout), nmaps, _pp(maps), _pp(wts),
+                     _pp(bcats), lib.int_array(chs + [0]), _ll(wstr + [0]), _ll(bstr + [0]), _pp(gbs) if keep else None,
+                     n, h, w, c, ldw, 0, act, up, lib.stream_ptr())
+        ctx.k3 = True
+        ctx.fast = False
+        ctx.nmaps, ctx.act = nmaps, act
+        ctx.batch_stats = bool(training or run_mean is None)
+        ctx.world = bn_sync_world(1) if ctx.batch_stats else 1
+        ctx.per_sample = [wg.dim() == 5 for wg in wgs]
+        ctx.save_for_backward(x, hout, mean, rstd, *maps, *wcats, *wts, *bcats, *gbs)
+        return hout
+
+    @staticmethod
+    def _backward_k3(ctx, dh):
+        """backward of the 3x3 form: gamma | beta of the forward (or, after a forward that kept no graph, recomputed by the
+        gather-GEMM) -> fsv_spade_bwd_elem -> d(gamma | beta); d(map) / d(W) as the data / weight gradient of ONE convolution with 2C
+        output channels (Geom(3, 3, 1, 1), per sample where the weights are generated), bias gradients as column sums"""
+        nm = ctx.nmaps
+        saved = ctx.saved_tensors
+        x, hout, mean, rstd = saved[:4]
+        maps = saved[4:4 + nm]
+        wcats = saved[4 + nm:4 + 2 * nm]
+        wts = saved[4 + 2 * nm:4 + 3 * nm]
+        bcats = saved[4 + 3 * nm:4 + 4 * nm]
+        gbs = list(saved[4 + 4 * nm:])
+        dh = to_nhwc(dh)
+        n, c, xs_h, xs_w = x.shape
+        up = ctx.up
+        h, w = (2 * xs_h, 2 * xs_w) if up else (xs_h, xs_w)
+        g3 = Geom(3, 3, 1, 1)
+        if len(gbs) != nm:
+            gbs = [conv_forward(maps[k], wts[k], wts[k].shape[-1], 2 * c, g3, bias=bcats[k], per_sample=ctx.per_sample[k])
+                   for k in range(nm)]
+        dxhat = empty_nhwc(n, c, h, w, x)
+        dgbs = [empty_nhwc(n, 2 * c, h, w, x) for _ in range(nm)]
+        lib.check_device(x, dh, hout, *gbs)
+        lib.call("fsv_spade_bwd_elem", lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(dh), lib.ptr(hout), nm,
+                 _pp(gbs), _pp(dgbs), lib.ptr(dxhat), n, h * w, c, 0, ctx.act, w, up, lib.stream_ptr())
+        dx = _SpadeFn._dx_from_dxhat(ctx, dxhat, x, mean, rstd, up)
+        grads = []
+        for k in range(nm):
+            base, ps = 7 + 5 * k, ctx.per_sample[k]
+            dm = dwg = dwb = dbg = dbb = None
+            if ctx.needs_input_grad[base]:
+                dm = conv_dgrad(dgbs[k], wcats[k], g3, (h, w), per_sample=ps)
+            if ctx.needs_input_grad[base + 1] or ctx.needs_input_grad[base + 2]:
+                dwcat = conv_wgrad(maps[k], dgbs[k], g3, tuple(wcats[k].shape), per_sample=ps)
+                dwg, dwb = torch.split(dwcat, c, dim=-4)
+            if ctx.needs_input_grad[base + 3] or ctx.needs_input_grad[base + 4]:
+                dbcat = colsum(dgbs[k], n, h * w, 2 * c) if ps else colsum(dgbs[k], 1, n * h * w, 2 * c).view(2 * c)
+                dbg, dbb = torch.split(dbcat, c, dim=-1)
+            grads += [dm, dwg, dwb, dbg, dbb]
+        return (None, None, None, None, dx, None, None, *grads)
+
+    @staticmethod
+    def _dx_from_dxhat(ctx, dxhat, x, mean, rstd, up):
+        n, c, xs_h, xs_w = x.shape
+        if not ctx.needs_input_grad[4]:
+            return None
+        if up:
+            pooled = empty_nhwc(n, c, xs_h, xs_w, dxhat)
+            lib.call("fsv_upsample2x_bwd", lib.ptr(dxhat), lib.ptr(pooled), n, xs_h, xs_w, c, lib.stream_ptr())
+            dxhat = pooled
+        if ctx.batch_stats:
+            dx, _, _ = bn_backward(dxhat, None, x, mean, rstd, None, 1, n * xs_h * xs_w, c, ACT_NONE, False, False, ctx.world)
+            return dx
+        return dxhat * rstd.view(1, c, 1, 1)
+
+    @staticmethod
     def backward(ctx, dh):
+        if getattr(ctx, 'k3', False):
+            return _SpadeFn._backward_k3(ctx, dh)
         nm = ctx.nmaps
         saved = ctx.saved_tensors
         x, hout, mean, rstd = saved[:4]

@@ -338,6 +338,17 @@ int fsv_spade_mod_bwd_h(const float* x, const float* mean, const float* rstd, co
 int fsv_spade_bwd_elem(const float* x, const float* mean, const float* rstd, const float* dh, const float* h,
                        int nmaps, const float* const* gb, float* const* dgb, float* dxhat,
                        int N, int HW, int C, long long stat_bstride, int act, int W, int up, fsv_stream_t stream);
+/* ---- SPADE with 3x3 gamma / beta convolutions (csrc/spade_k3.hip) - normalization.py:18-52 with --spade_ks 3 -----------------
+ * h = act( (...((x - mean) * rstd) * (1 + g_0) + b_0 ...) * (1 + g_{n-1}) + b_{n-1} ),  [g_k | b_k] = conv3x3(map_k, pad 1) + bcat_k,
+ * one launch for 0..3 maps.  x [N][H W][C] (up != 0: [N][H/2 W/2][C], read through the nearest x2 index; H, W even), maps[k]
+ * [N][H W][ch_k] (ch_k % 4 == 0), wt[k] = K-major forward operand of the combined weight [2C][ch_k][3][3] (fsv_prep_weight mode 0:
+ * rows tap * ch_k + ci, ldw >= 2C columns, gamma in [0, C), beta in [C, 2C)) + z * w_bstride[k] (0: shared by the batch), bcat[k]
+ * [2C] + z * b_bstride[k].  C % 4 == 0.  gb (optional, NULL or nmaps pointers): [N][H W][2C] gamma | beta of every map, the operand
+ * of fsv_spade_bwd_elem. */
+int fsv_spade_k3_fwd(const float* x, const float* mean, const float* rstd, float* h, int nmaps, const float* const* maps,
+                     const float* const* wt, const float* const* bcat, const int* ch, const long long* w_bstride,
+                     const long long* b_bstride, float* const* gb, int N, int H, int W, int C, int ldw, long long stat_bstride,
+                     int act, int up, fsv_stream_t stream);
 
 /* ---- measurement only (csrc/stamp.hip): device-side time stamps, graph-capturable brackets for bench.py's roofline object ----
  * fsv_stamp: *slot = the GPU's constant-rate wall clock when the stream reaches this point; fsv_stamp_rate_khz: its rate. */
