@@ -217,19 +217,37 @@ class SPADE(nn.Module):
         return ops.spade_mod(x, use_maps, use_w, rm, rv, act=act, training=self.training, up=up)
 
 
-class SPADEResnetBlock(nn.Module):
-    """Reference architecture.py:71-108 (conv_params_free=False; SPADE or plain-BatchNorm flavour)."""
+class AdaptiveConv2d(nn.Module):
+    """architecture.py:31-35 (--adaptive_conv): a convolution without parameters of its own - weight [B, Cout, Cin, k, k] and bias
+    [B, Cout] come from the weight generators, one set per sample (ops.batch_conv, padding k // 2)"""
 
-    def __init__(self, fin, fout, hidden_nc=0, spade=True, norm_params_free=False, spade_ks=1):
+    def forward(self, x, act=ACT_NONE, res=None, stats=0, wb=None):
+        # (stats: the BatchNorm-statistics epilogue is a shared-weight launch's; the normalisation that follows reduces itself)
+        if wb is None:
+            raise ValueError("a parameter-free convolution needs generated weights (conv_weights)")
+        return ops.batch_conv(x, wb[0], wb[1], act=act, res=res)
+
+
+class SPADEResnetBlock(nn.Module):
+    """Reference architecture.py:71-108 (SPADE or plain-BatchNorm flavour).  conv_params_free (--adaptive_conv): conv_0, conv_1 and
+    conv_s own no parameters and no spectral norm; forward() takes their per-sample [weight, bias] pairs as `conv_weights`."""
+
+    def __init__(self, fin, fout, hidden_nc=0, spade=True, norm_params_free=False, spade_ks=1, conv_params_free=False):
         super().__init__()
         self.spade_ks = spade_ks
         fhidden = min(fin, fout)
         self.learned_shortcut = fin != fout
         self.spade = spade
-        self.conv_0 = Conv2d(fin, fhidden, 3, padding=1, spectral=True)
-        self.conv_1 = Conv2d(fhidden, fout, 3, padding=1, spectral=True)
-        if self.learned_shortcut:
-            self.conv_s = Conv2d(fin, fout, 1, bias=False, spectral=True)
+        self.conv_params_free = conv_params_free
+        if conv_params_free:
+            self.conv_0, self.conv_1 = AdaptiveConv2d(), AdaptiveConv2d()
+            if self.learned_shortcut:
+                self.conv_s = AdaptiveConv2d()          # (its generated form HAS a bias: generator.py:288)
+        else:
+            self.conv_0 = Conv2d(fin, fhidden, 3, padding=1, spectral=True)
+            self.conv_1 = Conv2d(fhidden, fout, 3, padding=1, spectral=True)
+            if self.learned_shortcut:
+                self.conv_s = Conv2d(fin, fout, 1, bias=False, spectral=True)
         if spade:
             self.bn_0 = SPADE(fin, hidden_nc, norm_params_free, spade_ks)
             self.bn_1 = SPADE(fhidden, hidden_nc, norm_params_free, spade_ks)
@@ -241,11 +259,19 @@ class SPADEResnetBlock(nn.Module):
             if self.learned_shortcut:
                 self.bn_s = BatchNorm(fin)
 
-    def forward(self, x, label=None, norm_weights=None, up=False, feeds_norm=True):
+    def _conv(self, name, x, wb, **kw):
+        m = getattr(self, name)
+        return m(x, wb=wb, **kw) if self.conv_params_free else m(x, **kw)
+
+    def forward(self, x, label=None, norm_weights=None, up=False, feeds_norm=True, conv_weights=None):
         """up=True: x is the block input BEFORE the nearest x2 up-sampling of generator.py:124.  With a learned shortcut
         the up-sampled tensor is consumed only by bn_0 and bn_s, which read x through the up-sampling index (ops.spade_mod
-        up=True) - it is never written; otherwise it is materialised here."""
+        up=True) - it is never written; otherwise it is materialised here.  conv_weights: [[weight, bias]] x 3 for conv_0, conv_1,
+        conv_s of a conv_params_free block.  The fused SPADE -> convolution launches are written for shared weights: handed a
+        per-sample convolution they decline (ops._spade_conv_s_fits / _spade_conv3_fits) and the held-back modulation runs as its
+        own launch."""
         nw = norm_weights if norm_weights else [None] * 3
+        cw = conv_weights if conv_weights else [None] * 3
         fold = up and self.spade and self.learned_shortcut and x.shape[1] % 16 == 0 and ops.spade_can_fold_upsample()
         if up and not fold:
             x = ops.upsample2x(x)
@@ -260,11 +286,11 @@ class SPADEResnetBlock(nn.Module):
                     with ops.spade_pair():
                         hs = self.bn_s(x, label, nw[2], act=ACT_NONE, up=fold)
                         h0 = self.bn_0(x, label, nw[0], act=ACT_LRELU, up=fold)
-                    x_s = self.conv_s(hs)
+                    x_s = self._conv('conv_s', hs, cw[2])
                 else:
                     # bn_s -> conv_s as ONE kernel where csrc/spade_conv.hip covers the widths (ops.spade_into_conv)
                     with (ops.spade_into_conv() if k1 else contextlib.nullcontext()):
-                        x_s = self.conv_s(self.bn_s(x, label, nw[2], act=ACT_NONE, up=fold))
+                        x_s = self._conv('conv_s', self.bn_s(x, label, nw[2], act=ACT_NONE, up=fold), cw[2])
                     h0 = None if conv3 else self.bn_0(x, label, nw[0], act=ACT_LRELU, up=fold)
             else:
                 x_s = x
@@ -277,15 +303,16 @@ class SPADEResnetBlock(nn.Module):
                 # round 6, opt-in (FSV_SPADE_CONV3=1): actvn(bn_*) -> 3x3 convolution as ONE kernel where csrc/spade_conv3.hip covers
                 # the widths (the modulated tensor stays in LDS); anything else falls through to the two launches
                 with ops.spade_into_conv(conv3=True):
-                    dx = self.conv_0(self.bn_0(x, label, nw[0], act=ACT_LRELU, up=fold), stats=hint)
+                    dx = self._conv('conv_0', self.bn_0(x, label, nw[0], act=ACT_LRELU, up=fold), cw[0], stats=hint)
                 with ops.spade_into_conv(conv3=True):
-                    return self.conv_1(self.bn_1(dx, label, nw[1], act=ACT_LRELU), res=x_s, stats=hint if feeds_norm else 0)
-            dx = self.conv_0(h0, stats=hint)
-            return self.conv_1(self.bn_1(dx, label, nw[1], act=ACT_LRELU), res=x_s, stats=hint if feeds_norm else 0)
+                    return self._conv('conv_1', self.bn_1(dx, label, nw[1], act=ACT_LRELU), cw[1], res=x_s,
+                                      stats=hint if feeds_norm else 0)
+            dx = self._conv('conv_0', h0, cw[0], stats=hint)
+            return self._conv('conv_1', self.bn_1(dx, label, nw[1], act=ACT_LRELU), cw[1], res=x_s, stats=hint if feeds_norm else 0)
         hint = 1 if self.training else 0
-        x_s = self.conv_s(self.bn_s(x)) if self.learned_shortcut else x
-        dx = self.conv_0(self.bn_0(x, act=ACT_LRELU), stats=hint)
-        return self.conv_1(self.bn_1(dx, act=ACT_LRELU), res=x_s, stats=hint if feeds_norm else 0)
+        x_s = self._conv('conv_s', self.bn_s(x), cw[2]) if self.learned_shortcut else x
+        dx = self._conv('conv_0', self.bn_0(x, act=ACT_LRELU), cw[0], stats=hint)
+        return self._conv('conv_1', self.bn_1(dx, act=ACT_LRELU), cw[1], res=x_s, stats=hint if feeds_norm else 0)
 
 
 def _decode_early():
@@ -429,18 +456,36 @@ def pick_ref(refs, ref_idx):
 
 
 class FewShotGenerator(nn.Module):
-    """Reference generator.py:20-454 for use_label_ref == 'mul', no KLD, no adaptive_conv; n_shot >= 1 (with more than one
-    reference image the attention module of generator.py:291-316 merges the reference features)."""
+    """Reference generator.py:20-454 without the KLD branch; n_shot >= 1 (with more than one reference image the attention module
+    of generator.py:291-316 merges the reference features).  use_label_ref 'mul' (two encoders, softmax-pooled channel products
+    feed the weight generators) or 'concat' (one encoder on [image | label], every weight generator reads a 32 x 32 adaptive
+    average pool of a feature map: ops.pool_rows); adaptive_conv (generated conv_0 / conv_1 / conv_s of the adaptive decoder
+    blocks) needs 'concat', as it does in the reference."""
+    POOL = 32            # generator.py:54 sh_fix = sw_fix
 
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
-        if getattr(opt, 'adaptive_conv', False) or getattr(opt, 'lambda_kld', 0) > 0:
-            raise NotImplementedError("adaptive_conv and the KLD branch are outside the hot-path scope")
+        if getattr(opt, 'lambda_kld', 0) > 0:
+            # the reference computes mu / logvar but its loss collector never reads them, and the forward pass draws randn noise
+            raise NotImplementedError("lambda_kld > 0: the KLD branch is outside the hot-path scope")
         self.n_shot = getattr(opt, 'n_shot', 1)
         self.n_downsample_A = getattr(opt, 'n_downsample_A', 2)
-        if getattr(opt, 'use_label_ref', 'mul') != 'mul' or getattr(opt, 'res_for_ref', False):
-            raise NotImplementedError("only use_label_ref='mul' with SPADEConv2d encoders is on the hot path")
+        use_label_ref = getattr(opt, 'use_label_ref', 'mul')
+        if use_label_ref not in ('mul', 'concat'):
+            raise NotImplementedError("use_label_ref = %r: only 'mul' and 'concat'" % (use_label_ref,))
+        if getattr(opt, 'res_for_ref', False):
+            raise NotImplementedError("res_for_ref: only SPADEConv2d reference encoders are on the hot path")
+        self.concat_label_ref = use_label_ref == 'concat'
+        self.adap_conv = bool(getattr(opt, 'adaptive_conv', False))
+        if self.adap_conv and not self.concat_label_ref:
+            # the reference builds the fc_conv_* MLPs for ch_out inputs but feeds them encoded_ref[i] with ch_in channels
+            # (generator.py:104,412) and fails in the first Linear
+            raise ValueError("--adaptive_conv needs --use_label_ref concat, as in the reference (its weight generators fail on "
+                             "the 'mul' encoding)")
+        exact = str(getattr(opt, 'amp', '') or '').lower() in ('', 'o0', 'fp32', 'f32')
+        if (self.concat_label_ref or self.adap_conv) and not exact:
+            raise NotImplementedError("use_label_ref = 'concat' / adaptive_conv under --amp (exact fp32 only)")
         if opt.conv_ks != 3:
             raise NotImplementedError("conv_ks = %r: only 3 (the reference hard-codes padding 1 and a 3x3 get_conv_weights)"
                                       % (opt.conv_ks,))
@@ -467,25 +512,35 @@ class FewShotGenerator(nn.Module):
         self.n_adaptive_layers = opt.n_adaptive_layers if opt.n_adaptive_layers != -1 else n
         self.n_fc_layers = opt.n_fc_layers
         input_nc = opt.label_nc if opt.label_nc != 0 else opt.input_nc
-        self.ref_img_first = SPADEConv2d(opt.output_nc, nf)
-        self.ref_label_first = SPADEConv2d(input_nc, nf)
+        concat = self.concat_label_ref
+        self.ref_img_first = SPADEConv2d(opt.output_nc + (input_nc if concat else 0), nf)
+        if not concat:
+            self.ref_label_first = SPADEConv2d(input_nc, nf)
         for i in range(n):
             setattr(self, 'ref_img_down_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2))
             setattr(self, 'ref_img_up_%d' % i, SPADEConv2d(ch[i + 1], ch[i]))
-            setattr(self, 'ref_label_down_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2))
-            setattr(self, 'ref_label_up_%d' % i, SPADEConv2d(ch[i + 1], ch[i]))
-        if self.adap_spade:
+            if not concat:
+                setattr(self, 'ref_label_down_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2))
+                setattr(self, 'ref_label_up_%d' % i, SPADEConv2d(ch[i + 1], ch[i]))
+        if self.adap_spade or self.adap_conv:
             for i in range(self.n_adaptive_layers):
                 ch_in, ch_out = ch[i], ch[i + 1]
                 ch_h = ch_hidden[i][0]
-                names = ['fc_spade_0', 'fc_spade_1', 'fc_spade_s']
-                sk2, ek2 = self.spade_ks ** 2, self.embed_ks ** 2          # generator.py:83-95
-                outs = [(ch_h * sk2 + 1) * 2, (ch_h * sk2 + 1) * (1 if ch_in != ch_out else 2), (ch_h * sk2 + 1) * 2]
-                if self.adap_embed:
-                    names.append('fc_spade_e')
-                    outs.append(ch_in * ek2 + 1)
+                names, outs = [], []
+                if self.adap_spade:
+                    names += ['fc_spade_0', 'fc_spade_1', 'fc_spade_s']
+                    sk2, ek2 = self.spade_ks ** 2, self.embed_ks ** 2          # generator.py:83-95
+                    outs += [(ch_h * sk2 + 1) * 2, (ch_h * sk2 + 1) * (1 if ch_in != ch_out else 2), (ch_h * sk2 + 1) * 2]
+                    if self.adap_embed:
+                        names.append('fc_spade_e')
+                        outs.append(ch_in * ek2 + 1)
+                if self.adap_conv:                                            # generator.py:96-101
+                    names += ['fc_conv_0', 'fc_conv_1', 'fc_conv_s']
+                    outs += [ch_out * 9 + 1, ch_in * 9 + 1, ch_out + 1]
+                # generator.py:104: under 'concat' every MLP reads one pooled POOL x POOL map per row
+                fc_in = ch_out if not concat else self.POOL * self.POOL
                 for name, fo in zip(names, outs):
-                    layers = [Linear(ch_out, ch_out), _Slot()]
+                    layers = [Linear(fc_in, ch_out), _Slot()]
                     for _ in range(1, self.n_fc_layers):
                         layers += [Linear(ch_out, ch_out), _Slot()]
                     layers += [Linear(ch_out, fo)]
@@ -495,7 +550,8 @@ class FewShotGenerator(nn.Module):
         for i in reversed(range(n + 1)):
             setattr(self, 'up_%d' % i, SPADEResnetBlock(ch[i + 1], ch[i], hidden_nc=ch_hidden[i], spade=True,
                                                        norm_params_free=(self.adap_spade and i < self.n_adaptive_layers),
-                                                       spade_ks=self.spade_ks))
+                                                       spade_ks=self.spade_ks,
+                                                       conv_params_free=(self.adap_conv and i < self.n_adaptive_layers)))
         self.conv_img = Conv2d(nf, 3, 3, padding=1)
         if self.n_shot > 1:                # generator.py:128-134: key / query encoders of the attention module
             self.atn_query_first = SPADEConv2d(input_nc, nf)
@@ -563,21 +619,34 @@ class FewShotGenerator(nn.Module):
         return [[parts[2 * j].reshape(b, cout, cin, k, k), parts[2 * j + 1]] for j in range(npairs)]
 
     _MLP_NAMES = ('fc_spade_e', 'fc_spade_0', 'fc_spade_1', 'fc_spade_s')
+    _CONV_MLP_NAMES = ('fc_conv_0', 'fc_conv_1', 'fc_conv_s')
 
     def _mlp_names(self):
         return self._MLP_NAMES if self.adap_embed else self._MLP_NAMES[1:]
 
-    def _mlp_bank(self, feats):
+    def _mlp_bank(self, feats, conv_feats=()):
         """All weight-generator MLPs of all adaptive levels, advanced layer by layer with one grouped launch per layer
         (ops.mlp_bank) instead of one small launch per Linear; {(name, level): FC output} or None when the grouped path does
-        not apply (no optimiser-owned layouts yet, narrow-operand modes, FSV_CONV_GROUPS=0)."""
-        rows = [f.reshape(f.shape[0] * f.shape[1], -1) for f in feats]
+        not apply (no optimiser-owned layouts yet, narrow-operand modes, FSV_CONV_GROUPS=0).  feats[i] feeds the fc_spade_* chains
+        of level i, conv_feats[i] the fc_conv_* chains; a tensor that feeds several levels enters the bank once (its gradient is
+        then summed inside it, in chain order)."""
+        rows, slot = [], {}
+
+        def rows_of(f):
+            if id(f) not in slot:
+                slot[id(f)] = len(rows)
+                rows.append(f.reshape(f.shape[0] * f.shape[1], -1))
+            return slot[id(f)]
         chains, keys = [], []
-        for i in range(len(feats)):
-            for name in self._mlp_names():
-                layers = getattr(self, '%s_%d' % (name, i))
-                chains.append((i, [layers[k] for k in range(0, len(layers), 2)]))
-                keys.append((name, i))
+        for i in range(max(len(feats), len(conv_feats))):
+            for names, fs in ((self._mlp_names(), feats), (self._CONV_MLP_NAMES, conv_feats)):
+                if i >= len(fs):
+                    continue
+                r = rows_of(fs[i])
+                for name in names:
+                    layers = getattr(self, '%s_%d' % (name, i))
+                    chains.append((r, [layers[k] for k in range(0, len(layers), 2)]))
+                    keys.append((name, i))
         outs = ops.mlp_bank(rows, chains)
         return None if outs is None else dict(zip(keys, outs))
 
@@ -600,6 +669,19 @@ class FewShotGenerator(nn.Module):
             f = mlp(name).view(b, -1)
             return self._pairs(f, 2, co, ch_h, self.spade_ks)
         return embedding_weights, [two('fc_spade_0', ch_out), two('fc_spade_1', ch_in), two('fc_spade_s', ch_out)]
+
+    def get_conv_weights(self, feat, i, fc=None):
+        """generator.py:276-289: [weight, bias] of conv_0 [ch_in <- ch_out, 3x3], conv_1 [ch_in <- ch_in, 3x3] and conv_s
+        [ch_in <- ch_out, 1x1] of block up_i.  reshape_weight reads the weight off the front of the flattened FC output and ch_in
+        biases off its end; the output is exactly that long, so the split of _pairs is the same"""
+        ch_in, ch_out = self.ch[i], self.ch[i + 1]
+        b = feat.shape[0]
+        rows = feat.reshape(b * feat.shape[1], -1) if fc is None else None
+
+        def one(name, ci, k):
+            f = (fc[(name, i)] if fc is not None else self._mlp(name, i, rows)).view(b, -1)
+            return self._pairs(f, 1, ch_in, ci, k)[0]
+        return [one('fc_conv_0', ch_out, 3), one('fc_conv_1', ch_in, 3), one('fc_conv_s', ch_out, 1)]
 
     def attention_encode(self, img, name):
         x = getattr(self, name + '_first')(img)
@@ -631,15 +713,22 @@ class FewShotGenerator(nn.Module):
         n = self.n_downsample_G
         # (the two encoders as parallel branches of the captured graph: +2 ... 3 ms in round 2, re-measured in round 6 on the final
         # kernels: 42.32 / 42.65 -> 43.50 / 43.51 ms per step - profiles/r06_step_ab_schedule.txt; not kept)
-        x = self.ref_img_first(img_ref)
-        xl = self.ref_label_first(label_ref)
+        concat = self.concat_label_ref
+        if concat:               # generator.py:342-345: one encoder on [image | label]
+            x = self.ref_img_first(ops.cat_channels([img_ref, label_ref]))
+            xl = None
+        else:
+            x = self.ref_img_first(img_ref)
+            xl = self.ref_label_first(label_ref)
         atn = atn_vis = ref_idx = None
         for i in range(n):
             x = getattr(self, 'ref_img_down_%d' % i)(x)
-            xl = getattr(self, 'ref_label_down_%d' % i)(xl)
+            if not concat:
+                xl = getattr(self, 'ref_label_down_%d' % i)(xl)
             if self.n_shot > 1 and i == self.n_downsample_A - 1:          # generator.py:359-366
                 x, atn, atn_vis = self.attention_module(x, label, label_ref)
-                xl, _, _ = self.attention_module(xl, None, None, atn)
+                if not concat:
+                    xl, _, _ = self.attention_module(xl, None, None, atn)
                 ref_idx = torch.argmax(atn.reshape(label.shape[0], self.n_shot, -1).sum(2), dim=1)
         self._atn = (atn_vis, ref_idx)
         if not encode:           # generator.py:370: test-time frames after the first re-use the cached weights
@@ -647,8 +736,21 @@ class FewShotGenerator(nn.Module):
         fi, fl = [x], [xl]
         for i in reversed(range(n)):
             fi.append(getattr(self, 'ref_img_up_%d' % i)(fi[-1]))
-            fl.append(getattr(self, 'ref_label_up_%d' % i)(fl[-1]))
+            if not concat:
+                fl.append(getattr(self, 'ref_label_up_%d' % i)(fl[-1]))
+        if concat:
+            return x, self._pooled_rows(fi[::-1])
         return x, self._pooled(fi, fl)
+
+    def _pooled_rows(self, feats):
+        """'concat': what the weight generators read is nn.AdaptiveAvgPool2d((32, 32)) of the encoder's feature maps themselves,
+        one row per channel (generator.py:248,278, reshape_embed_input).  One pooled tensor [b, c, 1024] per feature map and pass,
+        shared by the fc_spade_* chains of level l - 1 and the fc_conv_* chains of level l (the reference pools the map once for
+        each; the values are the same); maps no generator reads are not pooled."""
+        n, nl = self.n_downsample_G, self.n_adaptive_layers
+        used = set(min(n, i + 1) for i in range(nl) if self.adap_spade) | set(min(n, i) for i in range(nl) if self.adap_conv)
+        return [ops.pool_rows(f, self.POOL, self.POOL).view(f.shape[0], f.shape[1], self.POOL * self.POOL) if l in used else None
+                for l, f in enumerate(feats)]
 
     @staticmethod
     def _pooled(fi, fl):
@@ -670,8 +772,8 @@ class FewShotGenerator(nn.Module):
         return enc[::-1]
 
     def weight_generation(self, img_ref, label_ref, label, t=0, label_maps_elsewhere=False):
-        """returns (x, label maps, SPADE weights); with `label_maps_elsewhere` the middle entry is the generated embedding
-        weights instead (label_embedding.encode_maps runs next to the flow network, forward() finishes with decode_maps)"""
+        """returns (x, label maps, SPADE weights, conv weights); with `label_maps_elsewhere` the second entry is the generated
+        embedding weights instead (label_embedding.encode_maps runs next to the flow network, forward() finishes with decode_maps)"""
         b, n, c, h, w = img_ref.shape
         img_ref, label_ref = img_ref.reshape(b * n, -1, h, w), label_ref.reshape(b * n, -1, h, w)
         # generator.py:370,403-416: at test time (isTrain False, one reference) the generated weights of frame 0 are kept
@@ -681,33 +783,44 @@ class FewShotGenerator(nn.Module):
         cut2 = getattr(self, 'bwd_cut2', None)
         if cut2 is not None and fresh and torch.is_grad_enabled():
             # second stage boundary (three-piece backward): what the reference encoders hand on - the deepest feature map and
-            # the pooled products the weight generators read - becomes detached leaves; the encoders' backward is the third piece
+            # the pooled products ('concat': the pooled rows, not the full-size maps) the weight generators read - becomes
+            # detached leaves; the encoders' backward is the third piece
             cut2.begin_forward()
             x, enc = cut2.split((x, enc))
         if fresh:
-            embed_w, norm_w = [], []
-            if self.adap_spade:
-                feats = [enc[min(len(enc) - 1, i + 1)] for i in range(self.n_adaptive_layers)]
-                fc = self._mlp_bank(feats)
-                for i in range(self.n_adaptive_layers):
-                    e, nw = self.get_SPADE_weights(feats[i], i, fc)
-                    embed_w.append(e)
-                    norm_w.append(nw)
+            embed_w, norm_w, conv_w = [], [], []
+            if self.adap_spade or self.adap_conv:
+                nl = self.n_adaptive_layers
+                feats = [enc[min(len(enc) - 1, i + 1)] for i in range(nl)] if self.adap_spade else []
+                conv_feats = [enc[min(len(enc) - 1, i)] for i in range(nl)] if self.adap_conv else []         # generator.py:412
+                fc = self._mlp_bank(feats, conv_feats)
+                for i in range(nl):
+                    if self.adap_spade:
+                        e, nw = self.get_SPADE_weights(feats[i], i, fc)
+                        embed_w.append(e)
+                        norm_w.append(nw)
+                    if self.adap_conv:
+                        conv_w.append(self.get_conv_weights(conv_feats[i], i, fc))
             if not self.opt.isTrain:
-                self._cached_weights = (embed_w, norm_w)
+                self._cached_weights = (embed_w, norm_w, conv_w)         # generator.py:415-416
         else:
-            embed_w, norm_w = self._cached_weights
+            embed_w, norm_w, conv_w = self._cached_weights
         embed_w = embed_w if self.adap_embed else None
         if label_maps_elsewhere:
-            return x, embed_w, norm_w
-        return x, self.label_embedding(label, weights=embed_w), norm_w
+            return x, embed_w, norm_w, conv_w
+        return x, self.label_embedding(label, weights=embed_w), norm_w, conv_w
 
     def forward_face(self, label, label_refs, img_refs, img_coarse):
         """generator.py:232-242 (the --refine_face generator): the decoder starts from the encoding of the COARSE face
         (compute_kld with img_coarse, generator.py:321-325: reference-image encoder applied to it) instead of the
         reference image's; SPADE weights still come from the reference crops."""
-        _, enc_label, norm_w = self.weight_generation(img_refs, label_refs, label)
-        x = self.ref_img_first(img_coarse)
+        if self.adap_conv:
+            # generator.py:232-238 hands the blocks no conv weights: their parameter-free convolutions return the input, and the
+            # reference stops at the first block whose channel counts differ
+            raise ValueError("--refine_face with --adaptive_conv: the reference's face generator passes no convolution weights")
+        _, enc_label, norm_w, _ = self.weight_generation(img_refs, label_refs, label)
+        # generator.py:321-325: under 'concat' the encoder reads [coarse face | label]
+        x = self.ref_img_first(ops.cat_channels([img_coarse, label]) if self.concat_label_ref else img_coarse)
         for i in range(self.n_downsample_G):
             x = getattr(self, 'ref_img_down_%d' % i)(x)
         for i in range(self.n_downsample_G, -1, -1):
@@ -812,16 +925,16 @@ class FewShotGenerator(nn.Module):
             self._maps_ready = None
 
             def generate_and_decode():
-                x, embed_w, norm_w = self.weight_generation(img_refs, label_refs, label, t=t, label_maps_elsewhere=True)
+                x, embed_w, norm_w, conv_w = self.weight_generation(img_refs, label_refs, label, t=t, label_maps_elsewhere=True)
                 ready = self._maps_ready            # (set by the flow branch, which streams.fork issues first)
                 if ready is None:
-                    return x, embed_w, norm_w, None
+                    return x, embed_w, norm_w, conv_w, None
                 ev, maps = ready
                 cur = torch.cuda.current_stream(label.device)
                 cur.wait_event(ev)
                 streams._record(maps, cur)
-                return x, embed_w, norm_w, self.label_embedding.decode_maps(maps, embed_w)
-            (x, embed_w, norm_w, enc_label), (flow, mask, warp, emb, maps) = streams.fork(label, [
+                return x, embed_w, norm_w, conv_w, self.label_embedding.decode_maps(maps, embed_w)
+            (x, embed_w, norm_w, conv_w, enc_label), (flow, mask, warp, emb, maps) = streams.fork(label, [
                 generate_and_decode,
                 lambda: self.flow_branch(label, label_refs[:, 0], img_refs[:, 0], prev, with_label_maps=True)])
             self._maps_ready = None
@@ -829,7 +942,7 @@ class FewShotGenerator(nn.Module):
                 enc_label = self.label_embedding.decode_maps(maps, embed_w)
             atn_vis, ref_idx = self._atn
         else:
-            x, enc_label, norm_w = self.weight_generation(img_refs, label_refs, label, t=t)
+            x, enc_label, norm_w, conv_w = self.weight_generation(img_refs, label_refs, label, t=t)
             atn_vis, ref_idx = self._atn
             label_ref, img_ref = pick_ref(label_refs, ref_idx), pick_ref(img_refs, ref_idx)
             flow, mask, warp, emb, _ = self.flow_branch(label, label_ref, img_ref, prev)
@@ -838,7 +951,7 @@ class FewShotGenerator(nn.Module):
             cut.begin_forward()
             # stage boundary (see BackwardCut): everything above is "stage 1", the decoder below is "stage 2"
             # (stage2_parameters)
-            x, enc_label, norm_w, flow, mask, warp, emb = cut.split((x, enc_label, norm_w, flow, mask, warp, emb))
+            x, enc_label, norm_w, conv_w, flow, mask, warp, emb = cut.split((x, enc_label, norm_w, conv_w, flow, mask, warp, emb))
             enc_label = list(enc_label)
         # --add_raw_output_loss (generator.py:195, 202-205, 227): the last n_sc_layers blocks run a second time on the label
         # embedding alone (no warped-image maps) - same modules, so their spectral norms and BatchNorm running statistics take a
@@ -850,13 +963,15 @@ class FewShotGenerator(nn.Module):
                 enc_label[i] = [enc_label[i]] + [e[i] if e is not None else None for e in emb]
         for i in range(self.n_downsample_G, -1, -1):
             nw = norm_w[i] if (self.adap_spade and i < self.n_adaptive_layers) else None
+            cw = conv_w[i] if (self.adap_conv and i < self.n_adaptive_layers) else None
             # generator.py:121-124: the nearest x2 up-sampling after block i + 1 is handed to block i (up=True), whose SPADE
             # kernels read through the up-sampling index
             if enc_raw is not None and i < self.n_sc_layers:
                 if i == self.n_sc_layers - 1:
                     x_raw = x
-                x_raw = getattr(self, 'up_%d' % i)(x_raw, enc_raw[i], nw, up=(i != self.n_downsample_G), feeds_norm=i > 0)
-            x = getattr(self, 'up_%d' % i)(x, enc_label[i], nw, up=(i != self.n_downsample_G), feeds_norm=i > 0)
+                x_raw = getattr(self, 'up_%d' % i)(x_raw, enc_raw[i], nw, up=(i != self.n_downsample_G), feeds_norm=i > 0,
+                                                   conv_weights=cw)
+            x = getattr(self, 'up_%d' % i)(x, enc_label[i], nw, up=(i != self.n_downsample_G), feeds_norm=i > 0, conv_weights=cw)
         img_raw = self.conv_img(ops.activation(x, ACT_LRELU), act=ACT_TANH)
         if not self.spade_combine:
             img_final = img_raw

@@ -1032,10 +1032,11 @@ def pooled_product(a, sm):
     return _PooledFn.apply(a, sm)
 
 
-def batch_conv(x, weight, bias=None, act=ACT_NONE, stride=1, allow_half=True):
+def batch_conv(x, weight, bias=None, act=ACT_NONE, stride=1, allow_half=True, res=None):
     """Per-sample 1x1 (or kxk) convolution with generated weights [B, Cout, Cin, k, k] (base_network.py:56-71);
     stride 1 or 2 (padding k // 2, as the reference).  allow_half=False: a call site that only borrows the kernel for a
-    batched matrix product (torch.bmm in the reference: softmax pooling, attention) and stays fp32 under `--amp`."""
+    batched matrix product (torch.bmm in the reference: softmax pooling, attention) and stays fp32 under `--amp`.  res: added
+    in the epilogue (the residual sum of a block whose conv_1 takes generated weights; linear epilogue only)."""
     if weight is None:
         return x
     k = weight.shape[-1]
@@ -1043,7 +1044,7 @@ def batch_conv(x, weight, bias=None, act=ACT_NONE, stride=1, allow_half=True):
     # weights / biases are usually strided views into the weight-generating FC's output: conv.prep_weight / gather_gemm
     # read them in place (sample stride), no copies here
     _note_grad_mode()
-    return _ConvFn.apply(x, weight, bias, None, None, None, None, geom, act, 1.0, False, 0, allow_half)
+    return _ConvFn.apply(x, weight, bias, res, None, None, None, geom, act, 1.0, False, 0, allow_half)
 
 
 # ------------------------------------------------------------------------------------------------ normalisation
@@ -2571,3 +2572,37 @@ class _AdaptiveAvgPoolFn(torch.autograd.Function):
 
 def adaptive_avgpool(x, oh, ow):
     return _AdaptiveAvgPoolFn.apply(x, int(oh), int(ow))
+
+
+class _PoolRowsFn(torch.autograd.Function):
+    """nn.AdaptiveAvgPool2d((oh, ow)) followed by reshape_embed_input (generator.py:248,278 + base_network.py:169-174): the NHWC
+    feature map -> channel-major rows [B * C, oh * ow], one launch each way (csrc/pool_rows.hip) - no NHWC pooled tensor and no
+    transposing copy in between"""
+
+    @staticmethod
+    def forward(ctx, x, oh, ow):
+        x = to_nhwc(x)
+        n, c, h, w = x.shape
+        rows = torch.empty((n * c, oh * ow), dtype=torch.float32, device=x.device)
+        lib.register_sigs({"fsv_pool_rows_fwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+                           "fsv_pool_rows_bwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]})
+        lib.check_device(x)
+        lib.call("fsv_pool_rows_fwd", lib.ptr(x), lib.ptr(rows), n, h, w, c, oh, ow, lib.stream_ptr())
+        ctx.dims = (n, c, h, w, oh, ow)
+        return rows
+
+    @staticmethod
+    def backward(ctx, drows):
+        n, c, h, w, oh, ow = ctx.dims
+        drows = drows.contiguous()
+        dx = empty_nhwc(n, c, h, w, drows)
+        lib.check_device(drows)
+        lib.call("fsv_pool_rows_bwd", lib.ptr(drows), lib.ptr(dx), n, h, w, c, oh, ow, lib.stream_ptr())
+        return dx, None, None
+
+
+def pool_rows(x, oh=32, ow=32):
+    """rows [B * C, oh * ow] of the adaptive average pool of x [B, C, H, W] (fp32; C a multiple of 4)"""
+    if x.dtype != torch.float32:
+        raise NotImplementedError("pool_rows: fp32 feature maps only (got %s)" % x.dtype)
+    return _PoolRowsFn.apply(x, int(oh), int(ow))

@@ -489,6 +489,13 @@ int fsv_avgpool3s2_bwd(const float* dy, float* dx, int N, int H, int W, int C, f
  * windows [floor(o in / out), ceil((o + 1) in / out)) as in ATen; the backward pass is a gather (no atomics) */
 int fsv_adaptive_avgpool_fwd(const float* x, float* y, int N, int H, int W, int C, int OH, int OW, fsv_stream_t stream);
 int fsv_adaptive_avgpool_bwd(const float* dy, float* dx, int N, int H, int W, int C, int OH, int OW, fsv_stream_t stream);
+/* csrc/pool_rows.hip - the same pooling straight into the operand of the weight generators under --use_label_ref concat
+ * (generator.py:248,278 + reshape_embed_input): NHWC fp32 map x [N][H][W][C] -> channel-major rows [N * C][OH * OW], and the rows'
+ * gradient back to the map's (a gather, no atomics, fixed summation order).  C a multiple of 4 (16-byte accesses), else
+ * FSV_ERR_BAD_ARG; the backward pass returns FSV_ERR_UNSUPPORTED where 128 map pixels span more than 40 pooled columns (never for
+ * OW <= 40) */
+int fsv_pool_rows_fwd(const float* x, float* rows, int N, int H, int W, int C, int OH, int OW, fsv_stream_t stream);
+int fsv_pool_rows_bwd(const float* drows, float* dx, int N, int H, int W, int C, int OH, int OW, fsv_stream_t stream);
 /* softmax over the contiguous channel dimension of [rows][C] (nn.Softmax(dim=1) at generator.py:384) */
 int fsv_softmax_rows_fwd(const float* x, float* y, long long rows, int C, fsv_stream_t stream);
 int fsv_softmax_rows_bwd(const float* dy, const float* y, float* dx, long long rows, int C, fsv_stream_t stream);

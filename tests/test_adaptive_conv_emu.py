@@ -1,0 +1,213 @@
+"""--use_label_ref concat / --adaptive_conv on the emulator: the pooled-row kernel (csrc/pool_rows.hip through ops.pool_rows) against
+torch, one D + G iteration and three inference frames of the product against fixtures minted from the unmodified reference, the
+checkpoint layout, the option combinations that raise, the shared-weight SPADE fusions declining a per-sample convolution, and the
+stage lists of the split backward pass.
+
+Mint the fixtures (needs the reference tree):   python tests/test_adaptive_conv_emu.py
+"""
+import contextlib
+import copy
+import json
+import os
+import sys
+
+import pytest
+import torch
+
+import adaptive_conv_checks as ac
+import model_checks as mc
+
+DEV = torch.device('cpu')
+LAYOUT = os.path.join(ac.GOLD, 'ref_state_layout_aconv.json')
+NEW = ' --adaptive_conv --use_label_ref concat'
+
+
+@pytest.mark.parametrize('case', ac.STEP_CASES)
+def test_step_reproduces_reference_iteration_emu(emu_lib, case):
+    ac.check_step(DEV, case)
+
+
+def test_inference_reuses_cached_conv_weights_emu(emu_lib):
+    ac.check_inference(DEV)
+
+
+def test_state_dict_layout_equals_reference():
+    ref = json.load(open(LAYOUT))
+    assert set(ref) == {'C3_pose_512_aconv_concat', 'C1_face_128_concat'}
+    for cfg, layout in ref.items():
+        opt = ac.opt_from_flags(layout['flags'])
+        M = mc._model()
+        with torch.device('meta'):
+            model = M.create_model(opt)
+        for net, want in ((model.netG, layout['netG']), (model.netD, layout['netD'])):
+            mine = {k: list(v.shape) for k, v in net.state_dict().items()}
+            assert set(mine) == set(want), (cfg, sorted(set(mine) ^ set(want))[:10])
+            bad = [k for k in want if mine[k] != want[k]]
+            assert not bad, (cfg, bad[:10])
+    g = ref['C3_pose_512_aconv_concat']['netG']
+    assert not [k for k in g if k.startswith('ref_label_')]
+    assert g['fc_conv_0_0.0.weight_orig'][1] == 1024 and g['ref_img_first.conv.weight_orig'][1] == 3 + 6
+    assert not [k for k in g if k.startswith(('up_0.conv_', 'up_3.conv_'))] and 'up_4.conv_0.weight_orig' in g
+
+
+def test_adaptive_conv_needs_concat():
+    net = mc._net()
+    with torch.device('meta'):
+        with pytest.raises(ValueError, match='reference'):
+            net.define_G(mc.tiny_opt(adaptive_conv=True))
+
+
+@pytest.mark.parametrize('kw,word', [(dict(lambda_kld=1.0), 'lambda_kld'), (dict(res_for_ref=True), 'res_for_ref'),
+                                     (dict(use_label_ref='concat', amp='O1'), 'amp'),
+                                     (dict(use_label_ref='concat', adaptive_conv=True, amp='O1'), 'amp'),
+                                     (dict(use_label_ref='add'), 'use_label_ref')])
+def test_options_that_still_raise(kw, word):
+    net = mc._net()
+    with torch.device('meta'):
+        with pytest.raises(NotImplementedError, match=word):
+            net.define_G(mc.tiny_opt(**kw))
+
+
+# ---- 5(a): window indices.  Sizes that shrink, stay, grow, are non-divisible and non-square
+@pytest.mark.parametrize('h,w', [(64, 64), (32, 32), (16, 16), (2, 2), (7, 5), (40, 72), (33, 97)])
+@pytest.mark.parametrize('c', [4, 8, 36])
+def test_pool_rows_windows_against_torch(emu_lib, h, w, c):
+    ac.check_pool_windows(DEV, 2, c, h, w)
+
+
+# ---- 5(b): random inputs against float64, the bar from torch's own fp32 error on the same inputs
+@pytest.mark.parametrize('b,c,h,w', [(2, 8, 64, 64), (1, 36, 33, 97), (2, 16, 16, 16), (1, 4, 128, 96), (2, 8, 7, 5)])
+def test_pool_rows_random_against_float64(emu_lib, b, c, h, w):
+    ac.check_pool_random(DEV, b, c, h, w)
+
+
+def test_pool_rows_refuses_channel_counts_off_the_vector_width(emu_lib):
+    from importlib import import_module
+    lib = import_module('few-shot-vid2vid_amd.lib')
+    with pytest.raises(lib.FsvError):
+        ac.pool_product(DEV, torch.randn(1, 6, 8, 8), torch.randn(6, 1024))
+
+
+def _conv_free_block(net, g):
+    """a conv_params_free block with a learned shortcut, 1x1 SPADE with weights of its own, and generated weights for it"""
+    torch.manual_seed(0)
+    blk = net.SPADEResnetBlock(64, 32, hidden_nc=8, spade=True, conv_params_free=True)
+    cw = [[torch.randn(2, 32, 64, 3, 3, generator=g) * 0.05, torch.randn(2, 32, generator=g) * 0.1],
+          [torch.randn(2, 32, 32, 3, 3, generator=g) * 0.05, torch.randn(2, 32, generator=g) * 0.1],
+          [torch.randn(2, 32, 64, 1, 1, generator=g) * 0.1, torch.randn(2, 32, generator=g) * 0.1]]
+    return blk, cw
+
+
+def test_conv_params_free_block_owns_no_convolution_parameters():
+    net = mc._net()
+    blk, _ = _conv_free_block(net, torch.Generator().manual_seed(1))
+    assert not [k for k in blk.state_dict() if k.startswith('conv_')]
+
+
+def test_conv_params_free_block_against_torch(emu_lib):
+    """architecture.py:92-108 with AdaptiveConv2d: per-sample F.conv2d with the generated bias - also on conv_s, whose fixed form
+    has none"""
+    import torch.nn.functional as F
+    net = mc._net()
+    g = torch.Generator().manual_seed(8)
+    blk, cw = _conv_free_block(net, g)
+    x = torch.randn(2, 64, 8, 8, generator=g)
+    label = torch.randn(2, 8, 8, 8, generator=g)
+    ref = copy.deepcopy(blk)
+    y = blk(x.contiguous(memory_format=torch.channels_last), label, conv_weights=cw)
+
+    def spade(m, t):
+        out = F.batch_norm(t, None, None, training=True, eps=1e-5)
+        return out * (1 + F.conv2d(label, m.mlp_gamma.weight, m.mlp_gamma.bias)) + F.conv2d(label, m.mlp_beta.weight, m.mlp_beta.bias)
+
+    def bconv(t, wb):
+        return torch.cat([F.conv2d(t[i:i + 1], wb[0][i], wb[1][i], padding=wb[0].shape[-1] // 2) for i in range(t.shape[0])])
+    x_s = bconv(spade(ref.bn_s, x), cw[2])
+    dx = bconv(F.leaky_relu(spade(ref.bn_0, x), 0.2), cw[0])
+    dx = bconv(F.leaky_relu(spade(ref.bn_1, dx), 0.2), cw[1])
+    want = x_s + dx
+    assert float((y - want).abs().max()) <= 1e-4 * float(want.abs().max())
+
+
+def test_fused_spade_launches_decline_a_per_sample_convolution(emu_lib, monkeypatch):
+    """bn_s -> conv_s (on by default), FSV_SPADE_CONV3 and FSV_SPADE_PAIR are written for shared convolution weights: with every
+    switch on, a conv_params_free block launches the held-back modulations on their own and gives the same output as with the
+    switches off"""
+    from importlib import import_module
+    net, lib = mc._net(), import_module('few-shot-vid2vid_amd.lib')
+    g = torch.Generator().manual_seed(7)
+    blk0, cw = _conv_free_block(net, g)
+    x = torch.randn(2, 64, 4, 4, generator=g)
+    label = torch.randn(2, 8, 8, 8, generator=g)
+    outs = []
+    for on in ('0', '1'):
+        for k in ('FSV_SPADE_CONV_S', 'FSV_SPADE_CONV3', 'FSV_SPADE_PAIR'):
+            monkeypatch.setenv(k, on)
+        seen, real = [], lib.call
+        monkeypatch.setattr(lib, 'call', lambda name, *a: (seen.append(name), real(name, *a))[1])
+        blk = copy.deepcopy(blk0)          # (a forward advances the running statistics)
+        outs.append(blk(x.contiguous(memory_format=torch.channels_last), label, up=True, conv_weights=cw).detach().clone())
+        monkeypatch.setattr(lib, 'call', real)
+        assert not [s for s in seen if s.startswith('fsv_spade_conv')], seen
+    assert torch.equal(outs[0], outs[1])
+
+
+KW = dict(warp_ref=True, spade_combine=True, remove_face_labels=True, fineSize=32, loadSize=32, n_downsample_G=3, n_adaptive_layers=2,
+          use_label_ref='concat', adaptive_conv=True)
+
+
+def test_every_generator_parameter_lies_in_one_stage():
+    net = mc._net()
+    with torch.device('meta'):
+        G = net.define_G(mc.tiny_opt(**KW))
+    s2, s3 = [id(p) for p in G.stage2_parameters()], [id(p) for p in G.stage3_parameters()]
+    assert len(set(s2)) == len(s2) and len(set(s3)) == len(s3) and not set(s2) & set(s3)
+    names = {id(p): n for n, p in G.named_parameters()}
+    assert set(s2) | set(s3) <= set(names)
+    stage1 = [n for i, n in names.items() if i not in set(s2) | set(s3)]
+    assert any(n.startswith('fc_conv_') for n in stage1) and any(n.startswith('fc_spade_') for n in stage1)
+    assert all(names[i].startswith(('up_', 'conv_img')) for i in s2)
+    assert all(names[i].startswith(('ref_img_', 'atn_')) for i in s3) and s3
+
+
+@pytest.mark.parametrize('pieces', [True, 3])
+def test_split_backward_equals_one_piece(emu_lib, pieces):
+    """two-piece / three-piece backward (the second boundary behind the pooled rows): the weights after three iterations equal the
+    one-piece loop's bit for bit, plain and through GraphedIteration"""
+    import graph_step_checks as gc
+    _, pG, pD, _ = gc._run(DEV, False, 3, 520, KW)
+    for graphed in (False, True):
+        _, qG, qD, _ = gc._run(DEV, graphed, 3, 520, KW, split=pieces)
+        assert qG.numel() == pG.numel()
+        assert float((torch.sort(qG)[0] - torch.sort(pG)[0]).abs().max()) == 0.0, graphed
+        assert float((qD - pD).abs().max()) == 0.0, graphed
+
+
+def mint():
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from oracle import make_golden as mg, ref_import
+    face, pose = mg.CONFIGS['face'], mg.CONFIGS['pose_combine']
+    flags = {'face_concat': face + ' --use_label_ref concat',
+             'face_aconv_concat': face + NEW,
+             'face_aconv_only_concat': face.replace(' --adaptive_spade', '') + NEW,
+             'pose_combine_aconv_concat': pose + NEW}
+    for name, f in flags.items():
+        mg.step(name, f)
+    mg.inference(ac.INFERENCE_CASE, pose + NEW)
+    res = {}
+    for cfg, lay in (('C3_pose_512_aconv_concat', mg.LAYOUT_CONFIGS['C3_pose_512'] + NEW),
+                     ('C1_face_128_concat', mg.LAYOUT_CONFIGS['C1_face_128'] + ' --use_label_ref concat')):
+        opt, model = ref_import.build_model(lay.split())
+        res[cfg] = dict(flags=lay, netG={k: list(v.shape) for k, v in model.netG.state_dict().items()},
+                        netD={k: list(v.shape) for k, v in model.netD.state_dict().items()})
+        del model
+    with open(LAYOUT, 'w') as fh:
+        json.dump(res, fh)
+    for p in [os.path.join(ac.GOLD, 'step_%s.pt' % n) for n in flags] + \
+            [os.path.join(ac.GOLD, 'inference_%s.pt' % ac.INFERENCE_CASE), LAYOUT]:
+        print(p, os.path.getsize(p), 'bytes')
+
+
+if __name__ == '__main__':
+    with contextlib.suppress(KeyboardInterrupt):
+        mint()
