@@ -13,7 +13,8 @@ import torch
 
 from . import lib, profile
 
-ACT_NONE, ACT_LRELU, ACT_TANH, ACT_SIGMOID, ACT_RELU, ACT_LRELU01, ACT_DLRELU = 0, 1, 2, 3, 4, 5, 6
+ACT_NONE, ACT_LRELU, ACT_TANH, ACT_SIGMOID, ACT_RELU, ACT_LRELU01, ACT_DLRELU = (
+    lib.ENUMS["FSV_ACT_" + k] for k in ("NONE", "LRELU", "TANH", "SIGMOID", "RELU", "LRELU01", "DLRELU"))
 
 # Arithmetic of the GEMM operands (csrc/conv_np.hip).  0: exact fp32 MFMA (default, the measured path);
 # 1: "f16" - operands rounded to half while staged through LDS, fp32 accumulate (the reference's --amp contract, needs the
@@ -203,35 +204,7 @@ def unprep_weight_grad(dwt, w_shape, geom, scale=None, out=None):
 
 
 # ------------------------------------------------------------------------------------------------ grouped launches
-class ConvDesc(ctypes.Structure):
-    """include/fsv2v.h fsv_conv_desc"""
-    _fields_ = ([(k, ctypes.c_void_p) for k in ('inp', 'wt', 'bias', 'res', 'out', 'wscale')] +
-                [(k, ctypes.c_int) for k in ('N', 'H', 'W', 'Cin', 'OH', 'OW', 'Cout', 'ntaps')] +
-                [('ty', ctypes.c_int * 16), ('tx', ctypes.c_int * 16)] +
-                [(k, ctypes.c_int) for k in ('sy', 'sx', 'outH', 'outW', 'osy', 'osx', 'ooy', 'oox', 'ldw',
-                                             'per_sample', 'act', 'accumulate')] +
-                [('scale', ctypes.c_float), ('w_bstride', ctypes.c_longlong), ('b_bstride', ctypes.c_longlong)])
-
-
-class WgradDesc(ctypes.Structure):
-    """include/fsv2v.h fsv_wgrad_desc"""
-    _fields_ = ([(k, ctypes.c_void_p) for k in ('inp', 'dout', 'dwt')] +
-                [(k, ctypes.c_int) for k in ('N', 'H', 'W', 'Cin', 'OH', 'OW', 'Cout', 'ntaps')] +
-                [('ty', ctypes.c_int * 16), ('tx', ctypes.c_int * 16)] +
-                [(k, ctypes.c_int) for k in ('sy', 'sx', 'ldw', 'Kpad', 'per_sample', 'reserved')] +
-                [('w_bstride', ctypes.c_longlong)])
-
-
-lib.register_sigs({
-    "fsv_conv_gather_group": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
-    "fsv_conv_wgrad_group": [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
-    "fsv_conv_group_plan": [ctypes.POINTER(ctypes.c_int)] * 4 + [ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
-    "fsv_conv_gather_fwd_stats": [ctypes.c_void_p] * 5 + [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int)] * 2 +
-                                 [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                       ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p,
-                                                       ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p],
-})
-
+ConvDesc, WgradDesc = lib.STRUCTS["ConvDesc"], lib.STRUCTS["WgradDesc"]
 GROUP_LIMIT = 64          # FSV_GROUP_LIMIT (csrc/conv_igemm.hip)
 _TILE_DIMS = {0: (128, 128), 1: (128, 64), 2: (128, 32), 4: (64, 64), 9: (64, 128)}
 _tls = threading.local()  # autograd runs backward on its own thread: the active group is per thread
@@ -610,7 +583,6 @@ def conv_forward(x, wt_f, ldw, cout, geom, bias=None, res=None, act=ACT_NONE, sc
 
 def planned(mz, cout, nchunks, nsamp, force_tile=-1, force_split=0):
     """(tile id, split-K factor) fsv_conv_gather_fwd will use for this launch (csrc/conv_igemm.hip fsv_conv_plan)"""
-    lib.register_sigs({"fsv_conv_plan": [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)] * 2})
     tile, nsplit = ctypes.c_int(0), ctypes.c_int(1)
     lib.call("fsv_conv_plan", mz, cout, nchunks, nsamp, force_tile, force_split, ctypes.byref(tile), ctypes.byref(nsplit))
     return tile.value, nsplit.value

@@ -795,23 +795,6 @@ static inline void fsv_h_pack_taps(const int* ty, const int* tx, int n, unsigned
   }
 }
 
-// One problem at the C ABI (include/fsv2v.h fsv_hconv_desc; ctypes mirror in few-shot-vid2vid_amd/conv.py) - MUST match both.
-struct fsv_hconv_desc {
-  const void* in; const void* wt; const float* bias; const void* res; void* out; const float* wscale;
-  float* ws;               // fp32 workspace of N*outH*outW*Cout elements for split-K launches with a half output (or NULL: never split)
-  double* stats;           // statistics partials (or NULL)
-  int N, H, W, Cin, OH, OW, Cout, ntaps;
-  int ty[16], tx[16];
-  int sy, sx, outH, outW, osy, osx, ooy, oox;
-  int Kpad, nrows;
-  int per_sample, act, accumulate;
-  int out_h, res_h;
-  int force_tile, force_split;
-  int stats_groups, stats_slots, stats_prezeroed;
-  float scale;
-  long long w_bstride, b_bstride;
-};
-
 // tile ids: 0 = 128x128, 1 = 128x64, 2 = 128x32, 4 = 64x64, 9 = 64x128 (pixels x output channels) as 4-wave workgroups,
 // 3 = 128x128 and 5 = 256x128 as 8-wave workgroups;
 // + 16: the same tile with two LDS buffers (loads one chunk ahead) instead of three

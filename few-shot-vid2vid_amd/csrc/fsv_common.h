@@ -24,23 +24,12 @@ static thread_local int fsv_launch_status = 0;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// ---- status codes of the C ABI (include/fsv2v.h) -----------------------------------------------------
-#define FSV_OK 0
-#define FSV_ERR_BAD_ARG (-1)
-#define FSV_ERR_UNSUPPORTED (-2)
-#define FSV_ERR_LAUNCH (-3)
-
-// activation codes used by fused epilogues
-#define FSV_ACT_NONE 0
-#define FSV_ACT_LRELU 1   // leaky_relu(x, 0.2)  (reference models/networks/architecture.py:15-17)
-#define FSV_ACT_TANH 2
-#define FSV_ACT_SIGMOID 3
-#define FSV_ACT_RELU 4      // VGG19 feature stack (models/networks/vgg.py)
-#define FSV_ACT_LRELU01 5   // leaky_relu(x, 0.1): FlowNet2 teacher (flownet2_pytorch/networks/submodules.py:16,39)
-// gather-GEMM epilogue only (V4 kernel): out = v * leaky_relu'(aux), aux = the `res` operand (the OUTPUT of the layer whose
-// pre-activation gradient this launch produces) - the act-backward pass of a Linear + LeakyReLU chain folded into the data
-// gradient that feeds it.  Same arithmetic as fsv_act_bwd_kernel: aux > 0 ? v : 0.2 * v.
-#define FSV_ACT_DLRELU 6
+// The C ABI itself: status codes (fsv_status), activation codes (fsv_act), descriptor structs and the declaration of every entry
+// point.  Each definition in this directory is compiled against its declaration, so a parameter list that drifts from the
+// header is a "conflicting types" error.  The definitions spell the stream as hipStream_t.
+#define FSV_STREAM_T_DEFINED
+typedef hipStream_t fsv_stream_t;
+#include "fsv2v.h"
 
 #ifdef FSV_EMU
 static inline int fsv_check_launch() {

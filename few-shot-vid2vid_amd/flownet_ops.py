@@ -13,15 +13,6 @@ import torch
 from . import lib
 from .conv import empty_nhwc, to_nhwc
 
-c_p, c_i, c_ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-c_llp = ctypes.POINTER(ctypes.c_longlong)
-lib.register_sigs({
-    "fsv_correlation_fwd": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
-    "fsv_resample2d_fwd": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_llp, c_llp, c_llp, c_p],
-    "fsv_channelnorm_fwd": [c_p, c_p, c_i, c_i, c_ll, c_ll, c_ll, c_ll, c_p],
-    "fsv_bilinear_resize_fwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_llp, c_llp, c_p],
-})
-
 
 def _no_grad(*ts):
     if torch.is_grad_enabled() and any(t.requires_grad for t in ts):

@@ -13,13 +13,6 @@ import torch
 
 from . import lib
 
-c_p, c_i = ctypes.c_void_p, ctypes.c_int
-lib.register_sigs({"fsv_wgrad_finalize": [c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p],
-                   "fsv_upload_i64": [c_p, c_p, c_i, c_p],
-                   "fsv_gather_add": [c_p, c_i, c_p, c_i, c_p],
-                   "fsv_colsum_plan": [c_i, c_i, ctypes.POINTER(c_i)],
-                   "fsv_colsum_grouped": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p]})
-
 DOT_CHUNK = 4096
 
 
@@ -59,7 +52,7 @@ class GradFinalizer:
             if capturing:
                 raise lib.FsvError("new bias-gradient job sequence inside a graph capture; run one eager step first")
             plans, tmap1, tmap2, off = [], [], [], 0
-            out = (c_i * 5)()
+            out = (ctypes.c_int * 5)()
             for j, (p_rows, c) in enumerate(shapes):
                 lib.call("fsv_colsum_plan", p_rows, c, out)
                 v, tx, nslabs, rpb, nch = [int(x) for x in out]

@@ -13,29 +13,7 @@ import torch
 from . import conv, lib, profile
 from .conv import (ACT_NONE, ACT_DLRELU, Geom, _ceil, empty_nhwc, to_nhwc)
 
-c_p, c_i, c_ll, c_f = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
-
-
-class HConvDesc(ctypes.Structure):
-    """include/fsv2v.h fsv_hconv_desc"""
-    _fields_ = ([(k, c_p) for k in ('inp', 'wt', 'bias', 'res', 'out', 'wscale', 'ws', 'stats')] +
-                [(k, c_i) for k in ('N', 'H', 'W', 'Cin', 'OH', 'OW', 'Cout', 'ntaps')] +
-                [('ty', c_i * 16), ('tx', c_i * 16)] +
-                [(k, c_i) for k in ('sy', 'sx', 'outH', 'outW', 'osy', 'osx', 'ooy', 'oox', 'Kpad', 'nrows', 'per_sample', 'act',
-                                    'accumulate', 'out_h', 'res_h', 'force_tile', 'force_split', 'stats_groups', 'stats_slots',
-                                    'stats_prezeroed')] +
-                [('scale', c_f), ('w_bstride', c_ll), ('b_bstride', c_ll)])
-
-
-lib.register_sigs({
-    "fsv_hconv_gather": [c_p, c_i, ctypes.POINTER(c_i), c_p],
-    "fsv_hconv_plan": [c_i] * 7 + [ctypes.POINTER(c_i)] * 2,
-    "fsv_hconv_wgrad": [c_p, c_p, c_p] + [c_i] * 7 + [c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_i] +
-                       [c_i, c_i, c_ll, c_i, c_i, c_i, c_i, c_p],
-    "fsv_hconv_prep_weight": [c_p, c_p, c_i, c_p],
-    "fsv_hconv_prep_weight_one": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
-    "fsv_cast_half": [c_p, c_p, c_ll, c_i, c_p],
-})
+HConvDesc = lib.STRUCTS["HConvDesc"]
 
 # tests: called as _launch_hook(kind, info) behind every launch ('conv': x, wh, kpad, nrows, cout, oh, ow, ty, tx, sy, sx, bias, res,
 # act, scale, per_sample, place, wscale, out; 'wgrad': x, dout, geom, per_sample, dwt) - tests/model_checks.verify_half_launches
@@ -109,7 +87,7 @@ class half_side_output:
 
 
 def planned(mz, cout, nchunks, nsamp, force_tile=-1, force_split=0, can_split=True):
-    tile, nsplit = c_i(0), c_i(1)
+    tile, nsplit = ctypes.c_int(0), ctypes.c_int(1)
     lib.call("fsv_hconv_plan", mz, cout, nchunks, nsamp, force_tile, force_split, 1 if can_split else 0, ctypes.byref(tile),
              ctypes.byref(nsplit))
     return tile.value, nsplit.value
@@ -157,8 +135,6 @@ def prep_weight_h(wt):
 def eligible(cin, per_sample=False):
     """layers the half kernels take: input channels a multiple of 8 (16-byte fragments)"""
     return cin % 8 == 0
-
-
 
 
 def gather_gemm_h(x, wh, kpad, nrows, cout, oh, ow, ty, tx, sy, sx, bias=None, res=None, act=ACT_NONE, scale=1.0,
@@ -232,7 +208,7 @@ def gather_gemm_h(x, wh, kpad, nrows, cout, oh, ow, ty, tx, sy, sx, bias=None, r
             part = torch.empty(groups * conv.STATS_SLOTS * cout * 2, dtype=torch.float64, device=x.device)
         d.stats, d.stats_groups, d.stats_slots = part.data_ptr(), groups, conv.STATS_SLOTS
         keep.append(part)
-    produced = c_i(0)
+    produced = ctypes.c_int(0)
     label = 'fsv_hconv_kernel<%s>' % H_TILE_NAMES[tile & 15]
     if profile.detail():
         label += ' M%d N%d K%d z%d split%d' % (mz, cout, nchunks * 64, nsamp, nsplit)
@@ -259,7 +235,7 @@ def issue_group(items):
         flops = sum(it[2] for it in chunk)
 
         def go(arr=arr, n=len(chunk), keep=keep):
-            lib.call("fsv_hconv_gather", ctypes.cast(arr, c_p), n, None, lib.stream_ptr())
+            lib.call("fsv_hconv_gather", arr, n, None, lib.stream_ptr())
         with profile.scope('fsv_hconv_group_kernel' if len(chunk) > 1 else chunk[0][1], flops, replay=go):
             go()
         if _launch_hook is not None:

@@ -6,6 +6,7 @@ sources, and only when the test-suite asks for it explicitly with ``FSV2V_EMU=1`
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -13,45 +14,75 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
 _is_emu = False
 
-c_p = ctypes.c_void_p
-c_i = ctypes.c_int
-c_ll = ctypes.c_longlong
-c_f = ctypes.c_float
-c_ip = ctypes.POINTER(ctypes.c_int)
-
-# name -> argtypes (all functions return int status; 0 == FSV_OK).  Order mirrors include/fsv2v.h.
-_SIGS = {
-    "fsv_conv_gather_fwd": [c_p, c_p, c_p, c_p, c_p,
-                            c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                            c_i, c_ip, c_ip, c_i, c_i,
-                            c_i, c_i, c_i, c_i, c_i, c_i,
-                            c_i, c_ll, c_ll, c_i,
-                            c_i, c_f, c_i, c_i, c_i, c_p, c_p, c_ll, c_i, c_p],
-    "fsv_conv_wgrad": [c_p, c_p, c_p,
-                       c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                       c_i, c_ip, c_ip, c_i, c_i,
-                       c_i, c_i, c_ll, c_i, c_i, c_i, c_i, c_i, c_p],
-    "fsv_bias_act": [c_p, c_p, c_ll, c_i, c_i, c_p],
-    # narrow-operand (--amp) variants, csrc/conv_np.hip: the same arguments plus `mode` before the stream
-    "fsv_conv_gather_fwd_np": [c_p, c_p, c_p, c_p, c_p,
-                               c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                               c_i, c_ip, c_ip, c_i, c_i,
-                               c_i, c_i, c_i, c_i, c_i, c_i,
-                               c_i, c_ll, c_ll, c_i,
-                               c_i, c_f, c_i, c_i, c_i, c_p, c_i, c_p],
-    "fsv_conv_wgrad_np": [c_p, c_p, c_p,
-                          c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                          c_i, c_ip, c_ip, c_i, c_i,
-                          c_i, c_i, c_ll, c_i, c_i, c_i, c_i, c_i, c_p],
-    "fsv_prep_weight_grouped": [c_p, c_p, c_p, c_p, c_p, c_i, c_p],
-    "fsv_prep_weight": [c_p, c_p, c_p, c_i, c_i,
-                        c_i, c_i, c_i, c_i, c_i, c_ip, c_ip,
-                        c_i, c_i, c_ll, c_ll, c_p],
-}
-
 
 class FsvError(RuntimeError):
     pass
+
+
+# ---- the binding is read from include/fsv2v.h: to add an entry point, declare it there and define it in csrc/ ----------------
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "fsv2v.h")
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double,
+            "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong}
+# the only renames: a member that is a Python keyword, and the class names the descriptor structs have always had in conv.py / hconv.py
+_PY_NAMES = {"in": "inp", "fsv_conv_desc": "ConvDesc", "fsv_wgrad_desc": "WgradDesc", "fsv_hconv_desc": "HConvDesc"}
+
+
+def _declarator(text, where):
+    """`const float* in` / `int ty[16]` / `ty[16]` -> (ctypes type or None when the text names no type, name, array length or 0)"""
+    m = re.fullmatch(r"\s*(.*?)\s*\b(\w+)\s*(?:\[(\d+)\])?\s*", text, re.S)
+    if not m:
+        raise FsvError("include/fsv2v.h: cannot read `%s` in %s" % (text.strip(), where))
+    base = " ".join(m.group(1).replace("*", " * ").split())
+    base = re.sub(r"\bconst ", "", base)
+    if not base:
+        ctype = None
+    elif base.endswith("*") or base == "fsv_stream_t":
+        ctype = ctypes.c_void_p
+    elif base in _SCALARS:
+        ctype = _SCALARS[base]
+    else:
+        raise FsvError("include/fsv2v.h: no ctypes type for `%s` in %s" % (text.strip(), where))
+    return ctype, m.group(2), int(m.group(3) or 0)
+
+
+def parse_header(path=HEADER):
+    """-> (name -> argtypes of every `int fsv_*(...);`, class name -> ctypes.Structure of every `typedef struct`, enumerator -> value).
+    Raises FsvError on anything it does not understand: it never guesses a type."""
+    with open(path) as f:
+        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
+    enums = {}
+    for body in re.findall(r"\benum\s+\w+\s*\{(.*?)\}", text, re.S):
+        for item in body.split(","):
+            name, value = item.split("=")
+            enums[name.strip()] = int(value)
+    structs = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", text, re.S):
+        fields = []
+        for stmt in filter(str.strip, body.split(";")):          # `int N, H;` / `int ty[16], tx[16];`: one type, several members
+            members = stmt.split(",")
+            ctype = _declarator(members[0], name)[0]
+            if ctype is None or (ctype is ctypes.c_void_p and len(members) > 1):
+                raise FsvError("include/fsv2v.h: cannot read `%s` in %s" % (stmt.strip(), name))
+            for member in members:
+                _, field, count = _declarator(member, name)
+                fields.append((_PY_NAMES.get(field, field), ctype * count if count else ctype))
+        pyname = _PY_NAMES.get(name, name)
+        structs[pyname] = type(pyname, (ctypes.Structure,), {"_fields_": fields, "__doc__": "include/fsv2v.h " + name})
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    sigs = {}
+    for ret, name, params in re.findall(r"([\w \t*]*?)\b(fsv_\w+)\s*\(([^()]*)\)\s*;", text):
+        if ret.strip() != "int" or name in sigs:
+            raise FsvError("include/fsv2v.h: `%s %s(...)` is not an int-returning entry point declared once" % (ret.strip(), name))
+        sigs[name] = [] if params.strip() == "void" else [_declarator(p, name)[0] for p in params.split(",")]
+        if None in sigs[name]:
+            raise FsvError("include/fsv2v.h: a parameter of %s has no type" % name)
+    if len(sigs) != len(re.findall(r"\bfsv_\w+\s*\(", text)):
+        raise FsvError("include/fsv2v.h: a declaration was not understood")
+    return sigs, structs, enums
+
+
+# _SIGS: name -> argtypes (all functions return int status; 0 == FSV_OK)
+_SIGS, STRUCTS, ENUMS = parse_header()
 
 
 def emu_requested():
@@ -79,17 +110,6 @@ def get_lib():
         fn.restype = ctypes.c_int
     _lib = lib
     return lib
-
-
-def register_sigs(sigs):
-    """Used by sibling modules to add entry points (keeps one table per kernel file small)."""
-    _SIGS.update(sigs)
-    global _lib
-    if _lib is not None:
-        for name, argtypes in sigs.items():
-            fn = getattr(_lib, name)
-            fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
 
 
 def is_emu():

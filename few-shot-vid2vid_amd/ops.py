@@ -23,75 +23,10 @@ from .conv import (ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, Geom, c
                    gather_gemm, launch_group,
                    prep_weight, to_nhwc, zeros_nhwc)
 
-c_p, c_i, c_ll, c_f = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
-c_llp = ctypes.POINTER(ctypes.c_longlong)
-c_pp = ctypes.POINTER(ctypes.c_void_p)
-c_ip = ctypes.POINTER(ctypes.c_int)
-
-lib.register_sigs({
-    "fsv_warp_fwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_llp, c_llp, c_llp, c_p],
-    "fsv_warp_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_llp, c_llp, c_llp, c_llp, c_llp, c_p],
-    "fsv_norm_stats": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p, c_p, c_f, c_p],
-    "fsv_norm_stats_rep": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p, c_p, c_f, c_i, c_p],
-    "fsv_norm_stats_fused": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p, c_p, c_f, c_i, c_p, c_p],
-    "fsv_norm_bwd_fused": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
-    "fsv_colsum_fused": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p],
-    "fsv_norm_apply": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p],
-    "fsv_norm_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
-    "fsv_norm_sums": [c_p, c_p, c_p, c_i, c_i, c_p],
-    "fsv_norm_stats_from_sums": [c_p, ctypes.c_double, c_p, c_p, c_i, c_f, c_p, c_p, c_f, c_p],
-    "fsv_norm_bwd_sums": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
-    "fsv_norm_bwd_apply": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p],
-    "fsv_colsum": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "fsv_spade_prep": [c_p, c_p, c_p, c_p, c_ll, c_ll, c_ll, c_ll, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
-    "fsv_spade_mod_fwd": [c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp,
-                          c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_i, c_p],
-    "fsv_spade_mod_fwd_h": [c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp,
-                            c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_i, c_p],
-    "fsv_spade_mod_bwd_h": [c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp, c_pp, c_p,
-                            c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_i, c_i, c_p],
-    "fsv_spade_mod_fwd2": [c_p, c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp,
-                           c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_i, c_i, c_p],
-    "fsv_spade_bwd_elem": [c_p, c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_p, c_i, c_i, c_i, c_ll, c_i, c_i, c_i, c_p],
-    "fsv_spade_mod_bwd": [c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp, c_pp, c_p,
-                          c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_i, c_p],
-    # x mean rstd h | nmaps maps wt bcat ch w_bstride b_bstride gb | N H W C ldw stat_bstride act up stream
-    "fsv_spade_k3_fwd": [c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp, c_pp,
-                         c_i, c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_p],
-    "fsv_spade_conv_s_supported": [c_i, c_i, c_i],
-    "fsv_spade_conv_s_fwd": [c_p, c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp,
-                             c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_p, c_i, c_i, c_p, c_p],
-    "fsv_spade_conv3_supported": [c_i, c_i, c_i],
-    # x mean rstd hs out | nmaps maps wg wb bg bb ch w_bstride b_bstride | N H W C ldw stat_bstride up act | wc ldwc Cout bias res wscale |
-    # stats stats_slots stats_prezeroed stream
-    "fsv_spade_conv3_fwd": [c_p, c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp,
-                            c_i, c_i, c_i, c_i, c_i, c_ll, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
-    "fsv_spade_conv_s_fwd_h": [c_p, c_p, c_p, c_p, c_p, c_i, c_pp, c_pp, c_pp, c_pp, c_pp, c_ip, c_llp, c_llp,
-                               c_i, c_i, c_i, c_ll, c_i, c_i, c_p, c_i, c_i, c_p, c_p],
-    "fsv_upsample2x_fwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "fsv_upsample2x_bwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "fsv_act_fwd": [c_p, c_p, c_ll, c_i, c_p],
-    "fsv_act_bwd": [c_p, c_p, c_p, c_ll, c_i, c_f, c_p, c_p],
-    "fsv_softmax_rows_fwd": [c_p, c_p, c_ll, c_i, c_p],
-    "fsv_softmax_rows_bwd": [c_p, c_p, c_p, c_ll, c_i, c_p],
-    "fsv_adam_step": [c_p, c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_p],
-    "fsv_adam_step_range": [c_p, c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_i, c_p],
-    "fsv_sn_power_iter": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p],
-    "fsv_sn_backward": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
-    "fsv_sn_power_iter_batched": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_f, c_p],
-})
-
-_ws_fn = None
-
 
 def _ws(g, p, c, like):
     """fp64 scratch for the two-stage column reductions; the size comes from the library's own launch plan."""
-    global _ws_fn
-    if _ws_fn is None:
-        _ws_fn = getattr(lib.get_lib(), "fsv_norm_workspace_doubles")
-        _ws_fn.argtypes = [c_i, c_i, c_i]
-        _ws_fn.restype = c_i
-    return torch.empty(max(int(_ws_fn(g, p, c)), 2), dtype=torch.float64, device=like.device)
+    return torch.empty(max(lib.call_status("fsv_norm_workspace_doubles", g, p, c), 2), dtype=torch.float64, device=like.device)
 
 
 def _ticket(like):
@@ -333,7 +268,6 @@ def _stats_from_producer(x, groups, pixels, channels, eps, run_mean, run_var, mo
     part, g, slots, p, c = st
     if (g, p, c) != (groups, pixels, channels):
         return None
-    lib.register_sigs({"fsv_norm_stats_finish": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_f, c_i, c_p]})
     mean = torch.empty(groups * channels, dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
     lib.check_device(x, run_mean, run_var)
@@ -691,8 +625,6 @@ def _tap_sums(w4, rows):
     return torch.mm(w4.reshape(cout * cin, 9), k).view(cout, cin, 4, 4)
 
 
-
-
 def _up_subpixel_forward(x, w4, cout, bias, act, scale, wscale, cached=None):
     """y = act((conv3x3(nearest_x2(x), W) * wscale + bias) * scale) without the up-sampled tensor AND without its redundant
     products: output pixel 2s + r (r in {0,1} per axis) sees x[s - 1], x[s] (r = 0: weights W0, W1 + W2) resp. x[s], x[s + 1]
@@ -788,7 +720,7 @@ def linear(x2d, weight, bias=None, act=ACT_NONE, sn=None):
 
 
 # ------------------------------------------------------------------------------------------------ banks of small MLPs
-ACT_DLRELU = 6       # FSV_ACT_DLRELU (include/fsv2v.h): gather-GEMM epilogue v * leaky_relu'(res)
+ACT_DLRELU = _conv.ACT_DLRELU       # gather-GEMM epilogue v * leaky_relu'(res)
 
 
 class _MlpBankFn(torch.autograd.Function):
@@ -916,7 +848,6 @@ class _MlpBankFn(torch.autograd.Function):
 def _sum_terms(jobs):
     """jobs: [(dst, [src ...])] dense fp32 tensors of equal numel per job (at most 8 jobs, any number of terms): dst = sum of
     its terms, left to right, in one launch per four terms (csrc/wgrad_finalize.hip fsv_sum_terms)"""
-    lib.register_sigs({"fsv_sum_terms": [c_p, c_p, c_p, c_p, c_i, c_p]})
     while jobs:
         dsts = (ctypes.c_void_p * len(jobs))(*[d.data_ptr() for d, _ in jobs])
         srcs = (ctypes.c_void_p * (4 * len(jobs)))()
@@ -1745,7 +1676,7 @@ class _SpadeFn(torch.autograd.Function):
                              arr(wb_p), arr(bg_p), arr(bb_p), lib.int_array(chs + [0]), _ll(wstr + [0]), _ll(bstr + [0]),
                              _pp(dgbs), lib.ptr(dxhat), n, h * w, c, 2 * c, 0, ctx.act, w, up, flags,
                              lib.ptr(dbsum) if dbsum is not None else None, _ll(zstr + [0]) if dbsum is not None else None,
-                             slots if dbsum is not None else 1, ctypes.c_longlong(n * nm * 2 * c), lib.stream_ptr())
+                             slots if dbsum is not None else 1, n * nm * 2 * c, lib.stream_ptr())
                     if dbsum is not None:
                         dbsum = dbsum.sum(0, dtype=torch.float32) if slots > 1 else dbsum[0].float()
                     if _hconv.launch_hook() is not None:
@@ -1934,10 +1865,6 @@ def resample(image, flow):
     return _WarpFn.apply(image, flow)
 
 
-lib.register_sigs({
-    "fsv_warp_compose_fwd": [c_p] * 8 + [c_i] * 5 + [c_llp] * 6 + [c_p],
-    "fsv_warp_compose_bwd": [c_p] * 12 + [c_i] * 5 + [c_llp] * 7 + [c_p],
-})
 COMPOSE_CONCAT, COMPOSE_BLEND = 0, 1
 
 
@@ -2018,13 +1945,6 @@ def adam_step(param, grad, m, v, state, beta1, beta2, eps, gscale=1.0, tick=None
                  float(beta1), float(beta2), float(eps), float(gscale), 1 if tick else 0, lib.stream_ptr())
 
 
-lib.register_sigs({
-    "fsv_amp_check": [c_p, c_ll, c_p, c_p],
-    "fsv_amp_adam": [c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_p],
-    "fsv_amp_update": [c_p, c_p],
-})
-
-
 def amp_adam_step(param, grad, m, v, state, scaler, beta1, beta2, eps, gscale=1.0):
     """Adam step of the fp16-operand mode (csrc/amp.hip): overflow test of the scaled gradients, the step with
     grad * gscale / scale (skipped when a gradient is not finite), and apex's scale update - all on the device."""
@@ -2042,18 +1962,6 @@ def amp_adam_step(param, grad, m, v, state, scaler, beta1, beta2, eps, gscale=1.
 
 
 # ------------------------------------------------------------------------------------------------ losses / packing / masks
-lib.register_sigs({
-    "fsv_l1_fwd": [c_p, c_p, c_f, c_p, c_i, c_i, c_ll, c_llp, c_llp, c_p, c_p, c_p, c_p],
-    "fsv_l1_bwd": [c_p, c_p, c_f, c_p, c_i, c_i, c_ll, c_llp, c_llp, c_p, c_p, c_p, c_p, c_p],
-    "fsv_wsum_fwd": [c_pp, ctypes.POINTER(ctypes.c_float), c_i, c_p, c_p],
-    "fsv_wsum_bwd": [ctypes.POINTER(ctypes.c_float), c_i, c_p, c_p, c_p],
-    "fsv_hinge_fwd": [c_p, c_ll, c_f, c_p, c_p, c_p, c_p],
-    "fsv_hinge_bwd": [c_p, c_ll, c_f, c_p, c_p, c_p],
-    "fsv_pack_d_input": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_ll, c_llp, c_llp, c_llp, c_llp, c_p],
-    "fsv_unpack_d_grad": [c_p, c_p, c_i, c_i, c_i, c_i, c_ll, c_p],
-    "fsv_pool15": [c_p, c_p, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_i, c_f, c_p],
-    "fsv_part_masks": [c_p, c_p, c_ll, c_ll, c_i, c_ll, c_ll, c_i, c_i, c_p],
-})
 
 
 def _dense4(t):
@@ -2260,10 +2168,6 @@ class _PackDFn(torch.autograd.Function):
         return None, None, dfake, None, None
 
 
-lib.register_sigs({"fsv_pack_d_x": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_ll, c_llp, c_llp, c_llp, c_llp, c_i, c_i, c_i, c_p],
-                   "fsv_unpack_d_grad_h": [c_p, c_p, c_i, c_i, c_i, c_i, c_ll, c_p]})
-
-
 def pack_d_input(ref, lab, fake, real, for_conv=False):
     return _PackDFn.apply(ref, lab, fake, real, for_conv)
 
@@ -2283,15 +2187,6 @@ def part_masks(pose_ch, g0=0, ngroups=9):
     lib.call("fsv_part_masks", lib.ptr(pose_ch), lib.ptr(y), b * t, h * w, t, pose_ch.stride(0), pose_ch.stride(1), g0, ngroups,
              lib.stream_ptr())
     return y
-
-
-lib.register_sigs({
-    "fsv_face_boxes": [c_p, c_ll, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
-    "fsv_crop_resize_fwd": [c_p, c_ll, c_ll, c_ll, c_ll, c_i, c_p, c_p, c_i, c_i, c_p],
-    "fsv_crop_resize_bwd": [c_p, c_p, c_p, c_ll, c_ll, c_ll, c_ll, c_i, c_i, c_i, c_p],
-    "fsv_paste_face_fwd": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_ll, c_p],
-    "fsv_paste_face_bwd": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-})
 
 
 def face_boxes(label, use_openpose, crop_smaller=0):
@@ -2379,16 +2274,6 @@ def pool15(x, mode, thresh=0.0):
     lib.call("fsv_pool15", lib.ptr(x), lib.ptr(y), n, h, w, x.stride(0), x.stride(2), x.stride(3),
              0 if mode == 'max_gt' else 1, float(thresh), lib.stream_ptr())
     return y
-
-
-lib.register_sigs({
-    "fsv_cat_put": [c_p, c_p, c_ll, c_i, c_ll, c_llp, c_i, c_i, c_p],
-    "fsv_pad_channels": [c_p, c_p, c_ll, c_i, c_ll, c_llp, c_i, c_p],
-    "fsv_pad_channels_h": [c_p, c_p, c_ll, c_i, c_ll, c_llp, c_i, c_p],
-    "fsv_cat_get": [c_p, c_p, c_ll, c_i, c_ll, c_i, c_i, c_p],
-    "fsv_blend_fwd": [c_p, c_p, c_p, c_p, c_i, c_i, c_ll, c_llp, c_llp, c_llp, c_p],
-    "fsv_blend_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_ll, c_llp, c_llp, c_llp, c_p],
-})
 
 
 class _CatFn(torch.autograd.Function):
@@ -2482,12 +2367,6 @@ def blend(a, b, mask):
     return _BlendFn.apply(a, b, mask)
 
 
-lib.register_sigs({
-    "fsv_maxpool2_fwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "fsv_maxpool2_bwd": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-})
-
-
 class _MaxPool2Fn(torch.autograd.Function):
     """nn.MaxPool2d(2, 2) of the VGG19 feature stack."""
 
@@ -2513,12 +2392,6 @@ class _MaxPool2Fn(torch.autograd.Function):
 
 def maxpool2(x):
     return _MaxPool2Fn.apply(x)
-
-
-lib.register_sigs({
-    "fsv_avgpool3s2_fwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "fsv_avgpool3s2_bwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-})
 
 
 class _AvgPool3s2Fn(torch.autograd.Function):
@@ -2584,8 +2457,6 @@ class _PoolRowsFn(torch.autograd.Function):
         x = to_nhwc(x)
         n, c, h, w = x.shape
         rows = torch.empty((n * c, oh * ow), dtype=torch.float32, device=x.device)
-        lib.register_sigs({"fsv_pool_rows_fwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
-                           "fsv_pool_rows_bwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]})
         lib.check_device(x)
         lib.call("fsv_pool_rows_fwd", lib.ptr(x), lib.ptr(rows), n, h, w, c, oh, ow, lib.stream_ptr())
         ctx.dims = (n, c, h, w, oh, ow)

@@ -60,8 +60,6 @@ def detail():
 # once more that way, replays it and prices the dominant kernel on the in-graph durations.
 _stamp = None          # dict(label, buf, n, cal) while a stamped capture is being recorded
 
-lib.register_sigs({"fsv_stamp": [ctypes.c_void_p, ctypes.c_void_p], "fsv_stamp_rate_khz": []})
-
 
 def stamp_begin(label, max_launches, device):
     global _stamp
@@ -135,7 +133,6 @@ def bracket_average(label):
 
 def thin_rule(mz, k):
     """csrc/conv_igemm.hip fsv_conv_thin: the size rule of the vector-ALU kernels for Cout <= 4 layers"""
-    lib.register_sigs({"fsv_conv_thin_rule": [ctypes.c_int] * 2})
     return lib.call_status("fsv_conv_thin_rule", int(mz), int(k)) == 1
 
 
@@ -147,7 +144,6 @@ def conv_label(mz, cout, nchunks, nsamp, vec4, force_tile=-1, force_split=0, thi
         if _detail:
             base += ' M%d N%d K%d' % (mz, cout, nchunks * 32)
         return base
-    lib.register_sigs({"fsv_conv_plan": [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)] * 2})
     tile, nsplit = ctypes.c_int(0), ctypes.c_int(1)
     lib.call("fsv_conv_plan", mz, cout, nchunks, nsamp, force_tile, force_split, ctypes.byref(tile), ctypes.byref(nsplit))
     base = 'fsv_conv_igemm_kernel<%s,V%d>' % (TILE_NAMES[tile.value], 4 if vec4 else 1)

@@ -25,7 +25,9 @@
 extern "C" {
 #endif
 
+#ifndef FSV_STREAM_T_DEFINED /* the kernel sources define it as hipStream_t before including this file; a pointer either way */
 typedef void* fsv_stream_t; /* hipStream_t */
+#endif
 
 enum fsv_status { FSV_OK = 0, FSV_ERR_BAD_ARG = -1, FSV_ERR_UNSUPPORTED = -2, FSV_ERR_LAUNCH = -3 };
 enum fsv_act { FSV_ACT_NONE = 0, FSV_ACT_LRELU = 1 /* leaky_relu(0.2), architecture.py:15-17 */, FSV_ACT_TANH = 2,
