@@ -814,7 +814,7 @@ static inline int fsv_h_tile_dims(int tile, int& bm, int& bn) {
 // FSV_HCONV_NBUF = 2 | 3: force the LDS buffer count of the tiles the plan picks (A/B runs; 0 / unset: the plan's own choice)
 static inline int fsv_h_nbuf() {
   static int v = -1;
-  if (v < 0) { const char* e = getenv("FSV_HCONV_NBUF"); v = e ? atoi(e) : 0; if (v != 2 && v != 3) v = 0; }
+  if (v < 0) { v = (int)fsv_env("FSV_HCONV_NBUF", 0); if (v != 2 && v != 3) v = 0; }
   return v;
 }
 
@@ -851,8 +851,7 @@ extern "C" int fsv_hconv_plan(int Mz, int Cout, int nchunks, int nsamp, int forc
   if (fsv_h_tile_dims(tile, bm, bn)) return -1;
   if (force_split <= 0) {
     const long long wgs = (long long)fsv_cdiv(Mz, bm) * fsv_cdiv(Cout, bn) * nsamp;
-    const char* det = getenv("FSV_DETERMINISTIC");
-    if (can_split && wgs < 192 && nchunks >= 16 && !(det && det[0] == '1')) {
+    if (can_split && wgs < 192 && nchunks >= 16 && fsv_env("FSV_DETERMINISTIC", 0) != 1) {
       nsplit = (int)((512 + wgs - 1) / wgs);
       if (nsplit > 8) nsplit = 8;
       if (nsplit > nchunks / 6) nsplit = nchunks / 6;
@@ -1058,9 +1057,8 @@ int fsv_hconv_wgrad(const void* in, const void* dout, float* dwt,
   else if (force_tile == 6) { bmk = 128; bn = 64; w8 = 1; }
   const long long blocks = (long long)fsv_cdiv(p.K, bmk) * fsv_cdiv(Cout, bn) * nsamp;
   int nsplit = 1;
-  const char* det = getenv("FSV_DETERMINISTIC");
   if (force_split > 0) nsplit = force_split;
-  else if (!(det && det[0] == '1')) {
+  else if (fsv_env("FSV_DETERMINISTIC", 0) != 1) {
     // (the 128x32 tile - 40 KB of LDS, four workgroups per CU - wants them all: 138 against 92 TFLOP/s on pix524288 N32 K288)
     const long long target = bn == 32 ? 1024 : 288;
     nsplit = (int)((target + blocks - 1) / blocks);

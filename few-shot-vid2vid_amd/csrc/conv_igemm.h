@@ -106,7 +106,6 @@ struct ConvP {
   long long res_bytes;                   // extent of the residual tensor when one descriptor covers it (else 0: loaded per element)
   float* part;                           // ordered split-K: split k stores its partial output at part + k * part_stride (else null:
   long long part_stride;                 // splits add into the zeroed output atomically)
-  int band;                              // XCD bands: an XCD owns a CONTIGUOUS run of (pixel tile, channel tile) pairs (conv_igemm.hip)
   int up;                                // 1: `in` is stored at HALF the resolution (H / 2 x W / 2) and read through the nearest x2
                                          // up-sampling index (y >> 1, x >> 1) - the up-sampled tensor (generator.py:124, 497-504, 541-572:
                                          // nn.Upsample in front of a 3x3 convolution) is never written; H, W stay the logical size

@@ -512,27 +512,10 @@ __device__ __forceinline__ void fsv_conv_igemm_body(const ConvP& p, const int bx
 // K4608 split 8 ran at 31 TFLOP/s against 65 with the finishing launch - the device-scope release every split workgroup pays (an L2
 // write-back on this part) costs more than the 16 us launch it saves.  profiles/r05_notes.md section 4; removed.)
 
-// XCD bands (round 4; the half-precision kernel's order, conv_h.hip): XCD x - the workgroups with linear id b % 8 == x - owns the
-// CONTIGUOUS run of tiles [start(x), start(x + 1)) in (pixel tile, channel tile) order with the channel tile fastest, so the pixel
-// tiles resident on one XCD are neighbours: the rows above and below that the 3x3 / 4x4 taps reach into are in the SAME L2.  With
-// the interleaved order above an XCD holds every eighth pixel tile and shares nothing between its resident tiles (PMC, round 3:
-// 213 - 265 MB fetched per launch for 67 MB of activations at the Cout <= 64 full-resolution layers).  No padding workgroups:
-// the first (total % 8) XCDs own one tile more.
-__device__ __forceinline__ void fsv_xcd_band(int nx, int ny, int& bx, int& by) {
-  const int total = nx * ny;
-  const int b = blockIdx.x + blockIdx.y * nx;
-  const int q = total >> 3, r = total & 7;
-  const int x = b & 7;
-  const int t = x * q + (x < r ? x : r) + (b >> 3);
-  by = t % ny;
-  bx = t / ny;
-}
-
 template <int BM, int BN, int WM, int WN, int PF = 1, bool AF = false, int DBG = 0, int MODE = 0, bool UP = false>
 __global__ __launch_bounds__(64 * WM * WN) void fsv_conv_igemm_kernel(ConvP p) {
   int bx, by;
-  if (p.band) fsv_xcd_band(gridDim.x, gridDim.y, bx, by);
-  else fsv_xcd_tile(gridDim.x, gridDim.y, bx, by);
+  fsv_xcd_tile(gridDim.x, gridDim.y, bx, by);
   fsv_conv_igemm_body<BM, BN, WM, WN, PF, AF, DBG, MODE, UP>(p, bx, by, (int)blockIdx.z);
 }
 
@@ -900,11 +883,11 @@ __device__ __forceinline__ void fsv_xcd_range(int& kt, int& nt, int& z) {
 
 // V4 kernel: both operands are pixel-major in HBM and in LDS ([32 pixels][columns], ds_write_b128 / ds_read_b32, conflict
 // free); two LDS buffers, one barrier per 32-pixel chunk, absent rows / columns are loaded at FSV_BUF_OOB.
-// PF: prefetch distance of the global loads in chunks of 32 pixels (see the forward kernel): 1 = one register set, the loads of
-// chunk c + 1 issued at the top of chunk c; 2 = two sets, the set stored behind the 12th MFMA was loaded a whole chunk earlier.
+// Prefetch distance 1 (see the forward kernel): one register set, the loads of chunk c + 1 issued at the top of chunk c and stored
+// behind the 12th MFMA.
 // (A form with the loads written straight into LDS - the forward kernel's LD - was built and measured in round 3: 2 ... 15 % SLOWER per
 // shape, +0.45 ms on the step: its whole trips of three chunks pad reductions that are split into pieces of 8 - 16 chunks.  Removed.)
-template <int BMK, int BN, int WM, int WN, bool COUT4, int PF = 1>
+template <int BMK, int BN, int WM, int WN, bool COUT4>
 __device__ __forceinline__ void fsv_conv_wgrad_body(const WgradP& p, const int kt, const int nt, const int bz) {
   constexpr int BK = FSV_BK;   // pixels per chunk
   constexpr int NT = 64 * WM * WN;
@@ -947,8 +930,7 @@ __device__ __forceinline__ void fsv_conv_wgrad_body(const WgradP& p, const int k
   const int c_begin = zk * cps;
   const int c_end = (c_begin + cps < p.pchunks) ? (c_begin + cps) : p.pchunks;
 
-  constexpr int NSET = PF >= 2 ? 2 : 1;
-  float4 areg[NSET][NPA], breg[NSET][NPB];
+  float4 areg[NPA], breg[NPB];
   unsigned aoff[NPA], boff[NPB];
   // Branch-free, incremental addressing (see the forward kernel): every A row of this thread walks the output pixels in
   // steps of 32; (n, oy, ox) are advanced with 32 / OW and 32 % OW and one conditional subtract per level - the host
@@ -1043,84 +1025,41 @@ __device__ __forceinline__ void fsv_conv_wgrad_body(const WgradP& p, const int k
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[s][i], fb[s][j], acc[i][j], 0, 0, 0);
   };
-  // one chunk: the loads issued at its top go into (lar, lbr); (sar, sbr) is the set stored into the other LDS buffer behind three
-  // quarters of its MFMAs - the same set for PF = 1, the one loaded a chunk earlier for PF = 2.  One barrier per chunk.  Chunks past
-  // c_end are past the descriptors (zeros) or another split's pixels; what the last iterations store is never used.
-  auto chunk = [&](int buf, float4 (&lar)[NPA], float4 (&lbr)[NPB], const float4 (&sar)[NPA], const float4 (&sbr)[NPB]) {
-    issue_loads(lar, lbr);
-    const float* a_src = As + buf * A_ST;
-    const float* b_src = Bs + buf * B_ST;
-    float fa[2][4][TM], fb[2][4][TN];
-    read_group(a_src, b_src, 0, fa[0], fb[0]);
-    FSV_SCHED_FENCE();
-    calc_offsets();
-    read_group(a_src, b_src, 1, fa[1], fb[1]);
-    FSV_SCHED_FENCE();
-    mma_group(fa[0], fb[0]);
-    FSV_SCHED_FENCE();
-    read_group(a_src, b_src, 2, fa[0], fb[0]);
-    FSV_SCHED_FENCE();
-    mma_group(fa[1], fb[1]);
-    FSV_SCHED_FENCE();
-    read_group(a_src, b_src, 3, fa[1], fb[1]);
-    FSV_SCHED_FENCE();
-    mma_group(fa[0], fb[0]);
-    FSV_SCHED_FENCE();
-    store_chunk(buf ^ 1, sar, sbr);
-    FSV_SCHED_FENCE();
-    mma_group(fa[1], fb[1]);
-    __syncthreads();
-  };
+  // one chunk: the loads issued at its top are stored into the other LDS buffer behind three quarters of its MFMAs.  One barrier
+  // per chunk.  The loads of the last iteration are past the descriptors (zeros) or another split's pixels and never used.
   if (c_begin < c_end) {
-    if constexpr (PF == 1) {
-      calc_offsets();
-      issue_loads(areg[0], breg[0]);
-      calc_offsets();
-      store_chunk(0, areg[0], breg[0]);
-      __syncthreads();
-      int buf = 0;
+    calc_offsets();
+    issue_loads(areg, breg);
+    calc_offsets();
+    store_chunk(0, areg, breg);
+    __syncthreads();
+    int buf = 0;
 #pragma unroll 1
-      for (int pc = c_begin; pc < c_end; ++pc) {
-        // (written out instead of calling chunk(): the instruction stream that was validated on hardware, 80 registers)
-        issue_loads(areg[0], breg[0]);
-        const float* a_src = As + buf * A_ST;
-        const float* b_src = Bs + buf * B_ST;
-        float fa[2][4][TM], fb[2][4][TN];
-        read_group(a_src, b_src, 0, fa[0], fb[0]);
-        FSV_SCHED_FENCE();
-        calc_offsets();
-        read_group(a_src, b_src, 1, fa[1], fb[1]);
-        FSV_SCHED_FENCE();
-        mma_group(fa[0], fb[0]);
-        FSV_SCHED_FENCE();
-        read_group(a_src, b_src, 2, fa[0], fb[0]);
-        FSV_SCHED_FENCE();
-        mma_group(fa[1], fb[1]);
-        FSV_SCHED_FENCE();
-        read_group(a_src, b_src, 3, fa[1], fb[1]);
-        FSV_SCHED_FENCE();
-        mma_group(fa[0], fb[0]);
-        FSV_SCHED_FENCE();
-        store_chunk(buf ^ 1, areg[0], breg[0]);
-        FSV_SCHED_FENCE();
-        mma_group(fa[1], fb[1]);
-        __syncthreads();
-        buf ^= 1;
-      }
-    } else {
+    for (int pc = c_begin; pc < c_end; ++pc) {
+      issue_loads(areg, breg);
+      const float* a_src = As + buf * A_ST;
+      const float* b_src = Bs + buf * B_ST;
+      float fa[2][4][TM], fb[2][4][TN];
+      read_group(a_src, b_src, 0, fa[0], fb[0]);
+      FSV_SCHED_FENCE();
       calc_offsets();
-      issue_loads(areg[0], breg[0]);
-      calc_offsets();
-      store_chunk(0, areg[0], breg[0]);
-      issue_loads(areg[1], breg[1]);
-      calc_offsets();
+      read_group(a_src, b_src, 1, fa[1], fb[1]);
+      FSV_SCHED_FENCE();
+      mma_group(fa[0], fb[0]);
+      FSV_SCHED_FENCE();
+      read_group(a_src, b_src, 2, fa[0], fb[0]);
+      FSV_SCHED_FENCE();
+      mma_group(fa[1], fb[1]);
+      FSV_SCHED_FENCE();
+      read_group(a_src, b_src, 3, fa[1], fb[1]);
+      FSV_SCHED_FENCE();
+      mma_group(fa[0], fb[0]);
+      FSV_SCHED_FENCE();
+      store_chunk(buf ^ 1, areg, breg);
+      FSV_SCHED_FENCE();
+      mma_group(fa[1], fb[1]);
       __syncthreads();
-#pragma unroll 1
-      for (int pc = c_begin; pc < c_end; pc += 2) {
-        chunk(0, areg[0], breg[0], areg[1], breg[1]);
-        if (pc + 1 >= c_end) break;
-        chunk(1, areg[1], breg[1], areg[0], breg[0]);
-      }
+      buf ^= 1;
     }
   }
 #pragma unroll
@@ -1140,11 +1079,11 @@ __device__ __forceinline__ void fsv_conv_wgrad_body(const WgradP& p, const int k
   }
 }
 
-template <int BMK, int BN, int WM, int WN, bool COUT4, int PF = 1>
+template <int BMK, int BN, int WM, int WN, bool COUT4>
 __global__ __launch_bounds__(64 * WM * WN) void fsv_conv_wgrad_kernel(WgradP p) {
   int kt, nt, bz;
   fsv_xcd_range(kt, nt, bz);
-  fsv_conv_wgrad_body<BMK, BN, WM, WN, COUT4, PF>(p, kt, nt, bz);
+  fsv_conv_wgrad_body<BMK, BN, WM, WN, COUT4>(p, kt, nt, bz);
 }
 
 // Grouped weight gradients (see fsv_conv_igemm_group_kernel): the problems' tiles in one 1-D grid, inside a problem ordered
@@ -1156,7 +1095,7 @@ struct WgradGroup {
   WgradP p[FSV_GROUP_MAX];
 };
 
-template <int BMK, int BN, int WM, int WN, bool COUT4, int PF = 1>
+template <int BMK, int BN, int WM, int WN, bool COUT4>
 __global__ __launch_bounds__(64 * WM * WN) void fsv_conv_wgrad_group_kernel(WgradGroup g) {
   const int b = blockIdx.x;
   int i = 0;
@@ -1165,7 +1104,7 @@ __global__ __launch_bounds__(64 * WM * WN) void fsv_conv_wgrad_group_kernel(Wgra
   const WgradP& p = g.p[i];
   const int gx = (p.K + BMK - 1) / BMK, gy = (p.Cout + BN - 1) / BN;
   const int r = t / gx;
-  fsv_conv_wgrad_body<BMK, BN, WM, WN, COUT4, PF>(p, t - r * gx, r % gy, r / gy);
+  fsv_conv_wgrad_body<BMK, BN, WM, WN, COUT4>(p, t - r * gx, r % gy, r / gy);
 }
 
 // scalar-gather twin (Cin % 4 != 0), single LDS buffer
@@ -1329,10 +1268,7 @@ __global__ __launch_bounds__(64 * WM * WN) void fsv_conv_wgrad_v1_kernel(WgradP 
 // order, but not the ascending-k chain of the MFMA path: these heads feed tanh / sigmoid / a scale, no LeakyReLU kink).
 // Host: Cin / 4 a power of two <= 64, K <= FSV_THIN_MAXK.
 #define FSV_THIN_MAXK 1152
-// T9 (round 6; the three heads of the step are 3x3): the lane's 9 x 4 x CO weights live in REGISTERS for the whole launch (they
-// depend on the lane's channel quad only - the loop used to re-read them from LDS for every pixel: 12 ds_reads per 12 fmas) and
-// the nine tap loads of a pixel are issued together; the fma chain of every output is the one of the generic loop (bit-equal).
-template <int CO, bool T9 = false>
+template <int CO>
 __global__ __launch_bounds__(256) void fsv_conv_thin_fwd_kernel(ConvP p, int iters) {
   __shared__ float wl[FSV_THIN_MAXK * CO];        // [k][co]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1348,18 +1284,6 @@ __global__ __launch_bounds__(256) void fsv_conv_thin_fwd_kernel(ConvP p, int ite
   const fsv_buf abuf = fsv_make_buf(p.in, (long long)p.N * p.H * p.W * p.Cin * 4);
   const float ws = p.wscale ? p.wscale[0] : 1.f;
   const int m_base = blockIdx.x * (4 * PPW * iters);
-  float wr[T9 ? 9 : 1][4][CO];
-  int tyr[T9 ? 9 : 1], txr[T9 ? 9 : 1];
-  if constexpr (T9) {
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      fsv_tap(p, t, tyr[t], txr[t]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int c = 0; c < CO; ++c) wr[t][e][c] = wl[(t * p.Cin + cq * 4 + e) * CO + c];
-    }
-  }
 #pragma unroll 1
   for (int it = 0; it < iters; ++it) {
     const int m = m_base + (it * 4 + wave) * PPW + pl;
@@ -1370,25 +1294,6 @@ __global__ __launch_bounds__(256) void fsv_conv_thin_fwd_kernel(ConvP p, int ite
     float acc[CO];
 #pragma unroll
     for (int c = 0; c < CO; ++c) acc[c] = 0.f;
-    if constexpr (T9) {
-      float4 v9[9];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int iy = oy * p.sy + tyr[t], ix = ox * p.sx + txr[t];
-        const bool ok = live & ((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W);
-        v9[t] = fsv_buf_load4(abuf, ok ? (unsigned)((((n * p.H + iy) * p.W + ix) * p.Cin + cq * 4) * 4) : FSV_BUF_OOB);
-      }
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-#pragma unroll
-        for (int c = 0; c < CO; ++c) {
-          acc[c] = fmaf(v9[t].x, wr[t][0][c], acc[c]);
-          acc[c] = fmaf(v9[t].y, wr[t][1][c], acc[c]);
-          acc[c] = fmaf(v9[t].z, wr[t][2][c], acc[c]);
-          acc[c] = fmaf(v9[t].w, wr[t][3][c], acc[c]);
-        }
-      }
-    } else
 #pragma unroll 3
     for (int t = 0; t < p.ntaps; ++t) {
       int ty, tx;
@@ -1501,9 +1406,9 @@ __global__ __launch_bounds__(256) void fsv_conv_thin_wgrad_kernel(WgradP p, int 
 // discriminator head with K = 8192 over 4900 pixels would be a handful of latency-bound work-items).  FSV_CONV_THIN (read at every
 // call: tests switch it): 0 = never, 2 = whenever the layer is eligible (unit tests on small maps), default = the size rule.
 static inline bool fsv_conv_thin(int Mz, int K) {
-  const char* e = getenv("FSV_CONV_THIN");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '2') return true;
+  const int sw = (int)fsv_env("FSV_CONV_THIN", 1);
+  if (sw == 0) return false;
+  if (sw == 2) return true;
   return K <= 1152 && (long long)Mz >= 64ll * K;
 }
 
@@ -1760,8 +1665,7 @@ static inline int fsv_conv_variant(int shape) {
     static const int dflt[10] = {16, 15, 18, -1, 20, -1, -1, -1, -1, 21};
     char name[16];
     snprintf(name, sizeof(name), "FSV_CONV_V%d", shape);
-    const char* e = getenv(name);
-    map[shape] = e ? atoi(e) : dflt[shape];
+    map[shape] = (int)fsv_env(name, dflt[shape]);
     if (map[shape] < 0) map[shape] = shape;
   }
   return map[shape];
@@ -1836,14 +1740,10 @@ static int fsv_launch_conv(const ConvP& p, bool vec4, int nz, hipStream_t stream
 static inline long long fsv_tune(int which) {
   static long long vals[4] = {-1, -1, -1, -1};
   if (vals[0] < 0) {
-    const char* a = getenv("FSV_SPLIT_BELOW");
-    const char* b = getenv("FSV_SPLIT_TARGET");
-    const char* c = getenv("FSV_WG_TARGET");
-    const char* d = getenv("FSV_WG_MINCH");
-    vals[1] = b ? atoll(b) : 512;
-    vals[2] = c ? atoll(c) : 1024;
-    vals[3] = d ? atoll(d) : 8;
-    vals[0] = a ? atoll(a) : 256;
+    vals[1] = (long long)fsv_env("FSV_SPLIT_TARGET", 512);
+    vals[2] = (long long)fsv_env("FSV_WG_TARGET", 1024);
+    vals[3] = (long long)fsv_env("FSV_WG_MINCH", 8);
+    vals[0] = (long long)fsv_env("FSV_SPLIT_BELOW", 256);
   }
   return vals[which];
 }
@@ -1874,12 +1774,10 @@ static inline double fsv_conv_cost(int Mz, int Cout, int nchunks, int nsamp, int
   // (FSV_SPLIT_FIX_US / FSV_SPLIT_BW_TBS: in-box A/B of the split's fixed cost and of the rate of its copies + finishing pass)
   static double split_fix = -1.0, split_bw = 0.0;
   if (split_fix < 0.0) {
-    const char* a = getenv("FSV_SPLIT_FIX_US");
-    const char* b = getenv("FSV_SPLIT_BW_TBS");
     // round 6: 3 us + 4.5 TB/s (6 us + 3.0 TB/s until the finishing pass became one vectorised pass: 15.6 -> 5.8 us per launch);
     // in-box: 42.86 -> 42.77 ms per step, the M2048 N512 K2304 layers now split in two (79.6 -> 94.0 TFLOP/s in isolation)
-    split_bw = (b ? atof(b) : 4.5) * 1e12;
-    split_fix = (a ? atof(a) : 3.0) * 1e-6;
+    split_bw = fsv_env("FSV_SPLIT_BW_TBS", 4.5) * 1e12;
+    split_fix = fsv_env("FSV_SPLIT_FIX_US", 3.0) * 1e-6;
   }
   if (nsplit > 1) t += split_fix + 0.5e-6 * nsplit + (double)Mz * Cout * nsamp * 4.0 * (2.0 + 0.25 * nsplit) / split_bw;
   return t;
@@ -1890,8 +1788,7 @@ static inline double fsv_conv_cost(int Mz, int Cout, int nchunks, int nsamp, int
 // that sit ON a LeakyReLU kink otherwise take the sign the atomics' order gives them (profiles/r02_notes.md section 11: one
 // weight gradient of the C1 step 3.6e-2 off in one run of eight).  Slower (small grids), never the measured configuration.
 static inline bool fsv_deterministic() {
-  const char* e = getenv("FSV_DETERMINISTIC");
-  return e && e[0] == '1';
+  return fsv_env("FSV_DETERMINISTIC", 0) == 1;
 }
 
 // size rule of the thin-output (vector-ALU) kernels, exported so that host-side profilers label those launches as what they
@@ -1937,14 +1834,6 @@ extern "C" int fsv_conv_plan(int Mz, int Cout, int nchunks, int nsamp, int force
   return 0;
 }
 
-// XCD order of the single-problem launches: 1 = bands (fsv_xcd_band), 0 = interleaved (fsv_xcd_tile); FSV_CONV_BAND: in-box A/B
-static inline int fsv_conv_band() {
-  static int v = -1;
-  // (measured in-box, profiles/r04_notes.md section 9: neutral on both bench steps - the interleaved order stays the default)
-  if (v < 0) { const char* e = getenv("FSV_CONV_BAND"); v = e ? (atoi(e) != 0) : 0; }
-  return v;
-}
-
 static inline void fsv_fill_convp(ConvP& p, const float* in, const float* wt, const float* bias, const float* res, float* out,
                                   const float* wscale, int N, int H, int W, int Cin, int OH, int OW, int Cout, int ntaps,
                                   const int* ty, const int* tx, int sy, int sx, int outH, int outW, int osy, int osx, int ooy,
@@ -1963,7 +1852,7 @@ static inline void fsv_fill_convp(ConvP& p, const float* in, const float* wt, co
   p.nsplit = 1;
   p.stats = nullptr; p.stats_slots = 1; p.stats_ohw = 1;
   p.part = nullptr; p.part_stride = 0;
-  p.band = fsv_conv_band(); p.up = 0;
+  p.up = 0;
   {
     const long long obytes = (long long)N * outH * outW * Cout * 4;
     p.res_bytes = (res && obytes <= FSV_BUF_MAX_BYTES) ? obytes : 0;
@@ -2007,19 +1896,11 @@ static int fsv_conv_gather_impl(const float* in, const float* wt, const float* b
     int iters = 16;
     while (iters > 1 && fsv_cdiv(p.Mz, ppb * iters) < 1024) iters >>= 1;
     const dim3 g(fsv_cdiv(p.Mz, ppb * iters));
-    // measured neutral on the step (profiles/r06_step_ab_kernel_tweaks.txt: 42.81 ms with, 42.74 without - the heads are bound by
-    // their L2 gathers, not by the LDS weight reads): opt-in, FSV_THIN_T9=1
-    const char* t9e = getenv("FSV_THIN_T9");
-    const bool t9 = p.ntaps == 9 && t9e && t9e[0] == '1';
     switch (Cout) {
-      case 1: if (t9) FSV_LAUNCH((fsv_conv_thin_fwd_kernel<1, true>), g, dim3(256), stream, p, iters);
-              else FSV_LAUNCH((fsv_conv_thin_fwd_kernel<1>), g, dim3(256), stream, p, iters); break;
-      case 2: if (t9) FSV_LAUNCH((fsv_conv_thin_fwd_kernel<2, true>), g, dim3(256), stream, p, iters);
-              else FSV_LAUNCH((fsv_conv_thin_fwd_kernel<2>), g, dim3(256), stream, p, iters); break;
-      case 3: if (t9) FSV_LAUNCH((fsv_conv_thin_fwd_kernel<3, true>), g, dim3(256), stream, p, iters);
-              else FSV_LAUNCH((fsv_conv_thin_fwd_kernel<3>), g, dim3(256), stream, p, iters); break;
-      default: if (t9) FSV_LAUNCH((fsv_conv_thin_fwd_kernel<4, true>), g, dim3(256), stream, p, iters);
-               else FSV_LAUNCH((fsv_conv_thin_fwd_kernel<4>), g, dim3(256), stream, p, iters); break;
+      case 1: FSV_LAUNCH((fsv_conv_thin_fwd_kernel<1>), g, dim3(256), stream, p, iters); break;
+      case 2: FSV_LAUNCH((fsv_conv_thin_fwd_kernel<2>), g, dim3(256), stream, p, iters); break;
+      case 3: FSV_LAUNCH((fsv_conv_thin_fwd_kernel<3>), g, dim3(256), stream, p, iters); break;
+      default: FSV_LAUNCH((fsv_conv_thin_fwd_kernel<4>), g, dim3(256), stream, p, iters); break;
     }
     return fsv_check_launch();
   }
@@ -2056,9 +1937,8 @@ static int fsv_conv_gather_impl(const float* in, const float* wt, const float* b
   // ... or from the finishing pass of an ordered K-split launch (fsv_split_finish4_stats_kernel)
   double* fin_stats = nullptr;
   {
-    const char* fse = getenv("FSV_SPLIT_FIN_STATS");       // =0: the consumer's own reduction pass (in-box A/B; read at every call)
-    const char* f4e = getenv("FSV_SPLIT_FIN4");
-    if (stats && !(fse && fse[0] == '0') && !(f4e && f4e[0] == '0') && nsplit > 1 && p.part && !accumulate && !per_sample && p.dense_out &&
+    // FSV_SPLIT_FIN_STATS=0: the consumer's own reduction pass (in-box A/B; read at every call)
+    if (stats && fsv_env("FSV_SPLIT_FIN_STATS", 1) != 0 && fsv_env("FSV_SPLIT_FIN4", 1) != 0 && nsplit > 1 && p.part && !accumulate && !per_sample && p.dense_out &&
         stats_groups >= 1 && stats_slots >= 1 && (Cout % 32) == 0 && p.Mz % stats_groups == 0 && ((p.Mz / stats_groups) % 32) == 0 &&
         act != FSV_ACT_DLRELU && !fsv_deterministic() &&
         (((unsigned long long)p.part | (unsigned long long)out | (unsigned long long)res) & 15ull) == 0) {
@@ -2076,8 +1956,8 @@ static int fsv_conv_gather_impl(const float* in, const float* wt, const float* b
     int grid = (int)((total + 256 * 8 - 1) / (256 * 8));
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;
-    const char* f4e = getenv("FSV_SPLIT_FIN4");          // =0: the scalar finishing pass (A/B, bit-equality test)
-    const bool fin4 = !(f4e && f4e[0] == '0') && p.part && (Cout % 4 == 0) && (total % 4 == 0) &&
+    // FSV_SPLIT_FIN4=0: the scalar finishing pass (A/B, bit-equality test)
+    const bool fin4 = fsv_env("FSV_SPLIT_FIN4", 1) != 0 && p.part && (Cout % 4 == 0) && (total % 4 == 0) &&
                       (((unsigned long long)p.part | (unsigned long long)out | (unsigned long long)res) & 15ull) == 0;
     if (fin_stats) {
       const long long npix = (long long)N * outH * outW;
@@ -2141,15 +2021,6 @@ int fsv_bias_act(float* x, const float* bias, long long total, int C, int act, h
   return fsv_check_launch();
 }
 
-// FSV_WGRAD_PF = 1 | 2: prefetch distance of the 64x64 and 128x32 weight-gradient kernels.  2 is opt-in: 128 / 144 registers
-// instead of 80 / 92 (3 instead of 5 - 6 waves per SIMD) for 49.12 / 49.30 vs 49.31 / 49.34 ms per step in-box (round 3, pass r3w)
-// - inside the noise of the pair.
-static inline int fsv_wgrad_pf() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("FSV_WGRAD_PF"); v = e ? atoi(e) : 1; if (v != 2) v = 1; }
-  return v;
-}
-
 int fsv_conv_wgrad(const float* in, const float* dout, float* dwt,
                    int N, int H, int W, int Cin, int OH, int OW, int Cout,
                    int ntaps, const int* ty, const int* tx, int sy, int sx,
@@ -2200,7 +2071,7 @@ int fsv_conv_wgrad(const float* in, const float* dout, float* dwt,
   else if (force_tile == 4 && vec4_ok(Cin) && Cout > 64) { bmk = 128; bn = 128; }
   long long target = fsv_tune(2);
   static int wplan_v = -1;
-  if (wplan_v < 0) { const char* e = getenv("FSV_WGRAD_PLAN"); wplan_v = e ? atoi(e) : 1; }
+  if (wplan_v < 0) wplan_v = (int)fsv_env("FSV_WGRAD_PLAN", 1);
   if (force_tile == 0 && wplan_v == 1 && vec4_ok(Cin) && Cout >= 64 && p.K > 64) {
     // in-box A/B on the step's layer shapes (tools/wgrad_ab.py, profiles/r02_wgrad_ab.jsonl): the 64x64 tile with ~2048
     // workgroups is best or within 2 % of the best on every shape (83 ... 111 TFLOP/s); 128-row tiles lose 10 ... 25 %
@@ -2230,11 +2101,9 @@ int fsv_conv_wgrad(const float* in, const float* dout, float* dwt,
     if (bn == 128 && bmk == 32) FSV_LAUNCH((fsv_conv_wgrad_kernel<32, 128, 1, 4, true>), g, block, stream, p);
     else if (bn == 128 && bmk == 64) FSV_LAUNCH((fsv_conv_wgrad_kernel<64, 128, 2, 2, true>), g, block, stream, p);
     else if (bn == 64 && bmk == 32) FSV_LAUNCH((fsv_conv_wgrad_kernel<32, 64, 1, 2, true>), g, dim3(128), stream, p);
-    else if (bn == 64 && bmk == 64 && fsv_wgrad_pf() == 2) FSV_LAUNCH((fsv_conv_wgrad_kernel<64, 64, 2, 2, true, 2>), g, block, stream, p);
     else if (bn == 64 && bmk == 64) FSV_LAUNCH((fsv_conv_wgrad_kernel<64, 64, 2, 2, true>), g, block, stream, p);
     else if (bn == 128) FSV_LAUNCH((fsv_conv_wgrad_kernel<128, 128, 2, 2, true>), g, block, stream, p);
     else if (bn == 64) FSV_LAUNCH((fsv_conv_wgrad_kernel<128, 64, 2, 2, true>), g, block, stream, p);
-    else if ((Cout & 3) == 0 && fsv_wgrad_pf() == 2) FSV_LAUNCH((fsv_conv_wgrad_kernel<128, 32, 4, 1, true, 2>), g, block, stream, p);
     else if ((Cout & 3) == 0) FSV_LAUNCH((fsv_conv_wgrad_kernel<128, 32, 4, 1, true>), g, block, stream, p);
     else FSV_LAUNCH((fsv_conv_wgrad_kernel<128, 32, 4, 1, false>), g, block, stream, p);
   } else {

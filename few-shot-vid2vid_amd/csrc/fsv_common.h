@@ -20,6 +20,7 @@ static thread_local int fsv_launch_status = 0;
   } while (0)
 #endif
 #include <stdint.h>
+#include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -54,3 +55,11 @@ __device__ __forceinline__ float fsv_act(float v, int act) {
 }
 
 static inline int fsv_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// The one place the library reads its environment: the numeric value of switch `name`, `dflt` when it is unset.  WHEN a switch is
+// read stays with its call site: once per process behind a function-local static, or at every call where tests toggle it at run
+// time (FSV_DETERMINISTIC, FSV_CONV_THIN, FSV_SPADE_MAX_GX, FSV_SPLIT_FIN4, FSV_SPLIT_FIN_STATS, FSV_S3_RW).
+static inline double fsv_env(const char* name, double dflt) {
+  const char* e = getenv(name);
+  return e ? atof(e) : dflt;
+}

@@ -234,8 +234,7 @@ static inline void fsv_red_no_tail(RedP& p) {
 static inline long long fsv_red_fuse_max_elems() {
   static long long v = -1;
   if (v < 0) {
-    const char* e = getenv("FSV_NORM_FUSE_MAX_MB");
-    double mb = e ? atof(e) : 1.0;
+    const double mb = fsv_env("FSV_NORM_FUSE_MAX_MB", 1.0);
     v = (long long)(mb * 1024.0 * 1024.0 / 4.0);
   }
   return v;
@@ -554,7 +553,7 @@ static inline int fsv_ew_grid(long long total) {
 
 static inline bool fsv_ew_vec4(long long total, int C) {
   static int on = -1;            // FSV_NORM_VEC4=0: in-box A/B switch (profiles/r02_notes.md section 13)
-  if (on < 0) { const char* e = getenv("FSV_NORM_VEC4"); on = (e && e[0] == '0') ? 0 : 1; }
+  if (on < 0) on = fsv_env("FSV_NORM_VEC4", 1) != 0 ? 1 : 0;
   return on && C % 4 == 0 && total < (1LL << 31);
 }
 

@@ -18,24 +18,23 @@
 #define FSV_SP_BK 32
 #define FSV_SP_MAXMAPS 3
 
-#define FSV_SP_SITES 2
 struct SpadeP {
   const float* x;         // [N][HW][C]
   const float* mean;      // [C] (or [N][C] when stat_bstride != 0)
   const float* rstd;
-  float* h[FSV_SP_SITES]; // [N][HW][C] per norm site
+  float* h;               // [N][HW][C]
   const float* map[FSV_SP_MAXMAPS];    // [N][HW][Ch_k]
-  const float* wg[FSV_SP_SITES][FSV_SP_MAXMAPS];     // K-major [Kpad_k][ldw] (+ z * w_bstride_k)
-  const float* wb[FSV_SP_SITES][FSV_SP_MAXMAPS];
-  const float* bg[FSV_SP_SITES][FSV_SP_MAXMAPS];     // [C] (+ z * b_bstride_k)
-  const float* bb[FSV_SP_SITES][FSV_SP_MAXMAPS];
+  const float* wg[FSV_SP_MAXMAPS];     // K-major [Kpad_k][ldw] (+ z * w_bstride_k)
+  const float* wb[FSV_SP_MAXMAPS];
+  const float* bg[FSV_SP_MAXMAPS];     // [C] (+ z * b_bstride_k)
+  const float* bb[FSV_SP_MAXMAPS];
   int ch[FSV_SP_MAXMAPS];
-  long long w_bstride[FSV_SP_SITES][FSV_SP_MAXMAPS];
-  long long b_bstride[FSV_SP_SITES][FSV_SP_MAXMAPS];
+  long long w_bstride[FSV_SP_MAXMAPS];
+  long long b_bstride[FSV_SP_MAXMAPS];
   int nmaps;
   int N, HW, C, ldw;
   long long stat_bstride;
-  int act[FSV_SP_SITES];
+  int act;
   // backward twin (BWD = true): upstream gradient in, d(gamma|beta) per map ([P][2C]: gamma columns [0, C), beta [C, 2C)) and
   // d(xhat) out; h is not written
   const float* dh;
@@ -62,9 +61,6 @@ __device__ __forceinline__ long long fsv_sp_xpix(const SpadeP& p, int z, int m) 
   return (long long)z * (p.HW >> 2) + (long long)(y >> 1) * (p.W >> 1) + (xx >> 1);
 }
 
-// NS norm sites per launch (NS = 2: bn_0 and bn_s of one SPADEResnetBlock, architecture.py:95-96,103 - the same x, the same
-// statistics, the same maps, their own gamma / beta weights and activation: x, the statistics and the label-map tiles are read
-// once for both, the map tile in LDS feeds four GEMMs instead of two).
 // BWD = true is the backward twin: the same two GEMMs recompute gamma / beta of every map in registers (they never reach HBM
 // in either direction), the forward chain o_0 = xhat, o_{k+1} = o_k (1 + g_k) + b_k is replayed keeping g_k and o_k, and the
 // epilogue walks it backwards:  d = dh * act'(o_n);  for k = n-1 .. 0:  dbeta_k = d,  dgamma_k = d * o_k,  d *= (1 + g_k);
@@ -73,7 +69,7 @@ __device__ __forceinline__ long long fsv_sp_xpix(const SpadeP& p, int z, int m) 
 //
 // Main loop (round 3: the structure of the gather-GEMM kernel, conv_igemm.hip).  The K chunks of ALL maps form one sequence
 // (the full-resolution levels have one or two 32-wide chunks per map: a per-map loop never gets a pipeline going): the loads of
-// chunk t + 1 - label-map rows and the gamma / beta weight rows of every site, through buffer descriptors with hardware zero
+// chunk t + 1 - label-map rows and the gamma / beta weight rows, through buffer descriptors with hardware zero
 // fill for rows / columns that do not exist - are issued at the top of chunk t and stored into the OTHER LDS buffer behind its
 // MFMAs (one barrier per chunk).  A image [BM rows][8 quads], quad q of row r in slot q ^ ((r >> 1) & 7): ds_write_b128 /
 // ds_read_b128 (two reads feed the four k steps of a k-group), B images [32 k][BN] as they lie in HBM.  The modulation of a
@@ -90,23 +86,21 @@ __device__ __forceinline__ long long fsv_sp_xpix(const SpadeP& p, int z, int m) 
 // ds_read_b128 fragments, csrc/conv_np.hip) staged through registers as 16-byte vectors; accumulation, normalisation, modulation and
 // the backward chain stay fp32.  At the deep levels (512 ... 2048 pixels, Ch up to 1024) the fp32 form is MFMA-latency bound - 128
 // workgroups, 32 chunks of 32 fp32 MFMAs each: 61 us for 4 GFLOP - which this removes.
-template <int BM, int BN, int WM, int WN, int NS, bool BWD, bool F16 = false, int NM = FSV_SP_MAXMAPS>
-__global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F16 || BM == 128) ? 3 : 4) void fsv_spade_mod_kernel(SpadeP p) {
+template <int BM, int BN, int WM, int WN, bool BWD, bool F16 = false, int NM = FSV_SP_MAXMAPS>
+__global__ __launch_bounds__(256, (BWD && NM > 1) ? 2 : (BWD || !F16 || BM == 128) ? 3 : 4) void fsv_spade_mod_kernel(SpadeP p) {
   constexpr int BK = FSV_SP_BK;
   // NM: the most maps this instantiation handles (the backward twin keeps g_k and o_k of every map in registers: 32 per map;
   // the one-map form - every layer without warp_ref / spade_combine - has room to keep the next tile's x and this tile's dh in
   // flight across the chunks, the three-map form requests them late)
-  constexpr bool XEARLY = NS == 1 && !BWD;
+  constexpr bool XEARLY = !BWD;
   constexpr bool DVEARLY = false;
   constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
   constexpr int RPA = 256 / 8, NPA = BM / RPA;          // A: 8 work-items per row (one quad of 4 k each)
   constexpr int QB = BN / 4, RPB = 256 / QB, NPB = BK / RPB;
-  constexpr int NB = NS * 2;                            // B images per chunk: (site, gamma | beta)
+  constexpr int NB = 2;                                 // B images per chunk: gamma | beta
   constexpr int A_ST = BM * BK, B_ST = BK * BN;
   static_assert(WM * WN == 4, "4 waves");
   static_assert(NPA >= 1 && NPB >= 1 && NPA * RPA == BM && NPB * RPB == BK, "tile");
-  static_assert(!BWD || NS == 1, "the backward twin handles one site");
-  static_assert(!F16 || NS == 1, "the half form handles one site");
   static_assert(FSV_SP_MAXMAPS == 3, "advance_loader selects among three maps");
   __shared__ __attribute__((aligned(16))) float smem[(F16 ? 1 : 2) * (A_ST + NB * B_ST)];
   float* const As = smem;
@@ -183,8 +177,7 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
   };
   // per-channel constants of this workgroup's channel tile, once: statistics and the gamma / beta biases of every map (a bias
   // loaded where it is used costs a full memory latency between the last MFMA of a map and its modulation)
-  constexpr bool BIAS_REGS = NS == 1;     // (the two-site form has no registers to spare: it loads the biases where it uses them)
-  float mu[TN], rs[TN], bgv[BIAS_REGS ? NS : 1][NM][TN], bbv[BIAS_REGS ? NS : 1][NM][TN];
+  float mu[TN], rs[TN], bgv[NM][TN], bbv[NM][TN];
   {
     const float* mean = p.mean + z * p.stat_bstride;
     const float* rstd = p.rstd + z * p.stat_bstride;
@@ -194,13 +187,11 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
       const bool cok = c < p.C;
       mu[j] = cok ? mean[c] : 0.f; rs[j] = cok ? rstd[c] : 0.f;
 #pragma unroll
-      for (int s = 0; s < (BIAS_REGS ? NS : 0); ++s)
-#pragma unroll
-        for (int k = 0; k < NM; ++k) {
-          const bool on = cok & (k < p.nmaps);
-          bgv[s][k][j] = on ? (p.bg[s][k] + z * p.b_bstride[s][k])[c] : 0.f;
-          bbv[s][k][j] = on ? (p.bb[s][k] + z * p.b_bstride[s][k])[c] : 0.f;
-        }
+      for (int k = 0; k < NM; ++k) {
+        const bool on = cok & (k < p.nmaps);
+        bgv[k][j] = on ? (p.bg[k] + z * p.b_bstride[k])[c] : 0.f;
+        bbv[k][j] = on ? (p.bb[k] + z * p.b_bstride[k])[c] : 0.f;
+      }
     }
   }
 
@@ -236,7 +227,7 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
     const long long wbytes = (long long)p.C * ldk * 2;            // one half (gamma or beta) of the operand: C rows of Kh halves
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
-      const h16* w = reinterpret_cast<const h16*>(q ? p.wb[0][k] : p.wg[0][k]) + z * p.w_bstride[0][k];
+      const h16* w = reinterpret_cast<const h16*>(q ? p.wb[k] : p.wg[k]) + z * p.w_bstride[k];
       const fsv_buf wbuf = fsv_make_buf(w, wbytes);
 #pragma unroll
       for (int i = 0; i < HNPB; ++i) {
@@ -278,17 +269,14 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
       areg[i] = fsv_buf_load4(abuf, ok ? (unsigned)((m * Ch + kk) * 4) : FSV_BUF_OOB);
     }
     const long long wbytes = (long long)((Ch + BK - 1) / BK) * BK * p.ldw * 4;
+    const fsv_buf gbuf = fsv_make_buf(p.wg[k] + z * p.w_bstride[k], wbytes);
+    const fsv_buf bbuf = fsv_make_buf(p.wb[k] + z * p.w_bstride[k], wbytes);
 #pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const fsv_buf gbuf = fsv_make_buf(p.wg[s][k] + z * p.w_bstride[s][k], wbytes);
-      const fsv_buf bbuf = fsv_make_buf(p.wb[s][k] + z * p.w_bstride[s][k], wbytes);
-#pragma unroll
-      for (int i = 0; i < NPB; ++i) {
-        const int kr = ld_c * BK + br0 + i * RPB;
-        const unsigned off = (live & bcol_ok) ? (unsigned)((kr * p.ldw + bcol) * 4) : FSV_BUF_OOB;
-        breg[2 * s][i] = fsv_buf_load4(gbuf, off);
-        breg[2 * s + 1][i] = fsv_buf_load4(bbuf, off);
-      }
+    for (int i = 0; i < NPB; ++i) {
+      const int kr = ld_c * BK + br0 + i * RPB;
+      const unsigned off = (live & bcol_ok) ? (unsigned)((kr * p.ldw + bcol) * 4) : FSV_BUF_OOB;
+      breg[0][i] = fsv_buf_load4(gbuf, off);
+      breg[1][i] = fsv_buf_load4(bbuf, off);
     }
     advance_loader();
   };
@@ -313,8 +301,8 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
         *reinterpret_cast<float4*>(&b_dst[q * B_ST + (br0 + i * RPB) * BN + bq * 4]) = breg[q][i];
   };
 
-  // running value of the normalised + modulated activation per site, in MFMA C/D layout
-  f32x16 outv[NS][TM][TN];
+  // running value of the normalised + modulated activation, in MFMA C/D layout
+  f32x16 outv[TM][TN];
   // backward twin: g_k and o_k of every map (BWD only; dead code otherwise)
   f32x16 keep_g[BWD ? NM : 1][TM][TN], keep_o[BWD ? NM : 1][TM][TN];
   f32x16 acc[NB][TM][TN];
@@ -366,39 +354,20 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
       }
   };
 
-  // modulation of map k: every site folds its gamma / beta accumulators into its running value and clears them
+  // modulation of map k: the gamma / beta accumulators are folded into the running value and cleared
   auto modulate = [&](int k, bool first) {
 #pragma unroll
-    for (int s = 0; s < NS; ++s) {
+    for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if constexpr (BIAS_REGS) {
+      for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float o = first ? (xv[i][j][r] - mu[j]) * rs[j] : outv[s][i][j][r];
-              const float gk = acc[2 * s][i][j][r] + bgv[s][k][j];
-              if constexpr (BWD) { keep_g[k][i][j][r] = gk; keep_o[k][i][j][r] = o; }
-              outv[s][i][j][r] = o * (1.f + gk) + (acc[2 * s + 1][i][j][r] + bbv[s][k][j]);
-              acc[2 * s][i][j][r] = 0.f; acc[2 * s + 1][i][j][r] = 0.f;
-            }
-        } else {
-          const int c = bn0 + wn * (TN * 32) + j * 32 + lrow;
-          const float bg_l = (c < p.C) ? (p.bg[s][k] + z * p.b_bstride[s][k])[c] : 0.f;
-          const float bb_l = (c < p.C) ? (p.bb[s][k] + z * p.b_bstride[s][k])[c] : 0.f;
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float o = first ? (xv[i][j][r] - mu[j]) * rs[j] : outv[s][i][j][r];
-              const float gk = acc[2 * s][i][j][r] + bg_l;
-              outv[s][i][j][r] = o * (1.f + gk) + (acc[2 * s + 1][i][j][r] + bb_l);
-              acc[2 * s][i][j][r] = 0.f; acc[2 * s + 1][i][j][r] = 0.f;
-            }
+        for (int r = 0; r < 16; ++r) {
+          const float o = first ? (xv[i][j][r] - mu[j]) * rs[j] : outv[i][j][r];
+          const float gk = acc[0][i][j][r] + bgv[k][j];
+          if constexpr (BWD) { keep_g[k][i][j][r] = gk; keep_o[k][i][j][r] = o; }
+          outv[i][j][r] = o * (1.f + gk) + (acc[1][i][j][r] + bbv[k][j]);
+          acc[0][i][j][r] = 0.f; acc[1][i][j][r] = 0.f;
         }
-      }
-    }
   };
 
   int buf = 0;
@@ -442,7 +411,7 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
     issue_loads();                      // past the end: every lane is out of range -> zeros, never used
     const float* a_src = As + buf * A_ST;
     const float* b_src = Bs + buf * (NB * B_ST);
-    if constexpr (NS == 1 && !BWD) {
+    if constexpr (!BWD) {
       // fragments one k-group ahead of their MFMAs (two register sets)
       float2 fa[2][2][TM];
       float fb[2][4][NB][TN];
@@ -464,7 +433,7 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
       FSV_SCHED_FENCE();
       mma_group(fa[1], fb[1]);
     } else {
-      // the two-site / backward forms carry 64 - 144 more live registers (four accumulators, or g_k / o_k of three maps):
+      // the backward form carries up to 144 more live registers (g_k / o_k of three maps):
       // one fragment set, two workgroups per CU cover each other's LDS latency
       float2 fa[2][TM];
       float fb[4][NB][TN];
@@ -541,13 +510,11 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
       }
     } else {
 #pragma unroll
-      for (int s = 0; s < NS; ++s)
+      for (int j = 0; j < TN; ++j)
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) outv[s][i][j][r] = (xv[i][j][r] - mu[j]) * rs[j];
+          for (int r = 0; r < 16; ++r) outv[i][j][r] = (xv[i][j][r] - mu[j]) * rs[j];
       if constexpr (XEARLY) load_x(bm0 + tile_step);
     }
     if constexpr (!DVEARLY) load_dv();
@@ -578,9 +545,9 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
             const bool ok0 = cok & (m < p.HW), ok1 = cok & (m + 1 < p.HW);
             float d0 = dv[i][j][r], d1 = dv[i][j][r + 1];
             if ((p.dbg & 1) && d0 != 1.2345e30f) { sb[0] += d0 * keep_o[0][i][j][r] + keep_g[0][i][j][r] + d1; continue; }
-            if (p.act[0] == FSV_ACT_LRELU) {
-              d0 = (outv[0][i][j][r] > 0.f) ? d0 : 0.2f * d0;
-              d1 = (outv[0][i][j][r + 1] > 0.f) ? d1 : 0.2f * d1;
+            if (p.act == FSV_ACT_LRELU) {
+              d0 = (outv[i][j][r] > 0.f) ? d0 : 0.2f * d0;
+              d1 = (outv[i][j][r + 1] > 0.f) ? d1 : 0.2f * d1;
             }
 #pragma unroll
             for (int k = NM - 1; k >= 0; --k) {
@@ -621,31 +588,28 @@ __global__ __launch_bounds__(256, (NS == 2 || (BWD && NM > 1)) ? 2 : (BWD || !F1
         }
       }
     } else {
+      float* h_z = p.h + pix0 * p.C;
+      h16* h_zh = reinterpret_cast<h16*>(p.h) + pix0 * p.C;
 #pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        float* h_z = p.h[s] + pix0 * p.C;
-        h16* h_zh = reinterpret_cast<h16*>(p.h[s]) + pix0 * p.C;
+      for (int j = 0; j < TN; ++j) {
+        const int c = bn0 + wn * (TN * 32) + j * 32 + lrow;
+        const bool cok = c < p.C;
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int c = bn0 + wn * (TN * 32) + j * 32 + lrow;
-          const bool cok = c < p.C;
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-              const int row = (r & 3) + 8 * (r >> 2) + 4 * lk;
-              const int m = bm0 + wm * (TM * 32) + i * 32 + row;
-              const bool ok0 = cok & (m < p.HW), ok1 = cok & (m + 1 < p.HW);
-              const float v0 = fsv_act(outv[s][i][j][r], p.act[s]), v1 = fsv_act(outv[s][i][j][r + 1], p.act[s]);
-              if ((p.dbg & 1) && v0 != 1.2345e30f) continue;
-              if (NS == 1 && p.h_half) {          // (the two-site form has no half output)
-                store_pair_h(h_zh, m * p.C + c, (m + 1) * p.C + c, v0, v1, ok0, ok1);
-              } else {
-                if (ok0) h_z[m * p.C + c] = v0;
-                if (ok1) h_z[(m + 1) * p.C + c] = v1;
-              }
+          for (int r = 0; r < 16; r += 2) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int m = bm0 + wm * (TM * 32) + i * 32 + row;
+            const bool ok0 = cok & (m < p.HW), ok1 = cok & (m + 1 < p.HW);
+            const float v0 = fsv_act(outv[i][j][r], p.act), v1 = fsv_act(outv[i][j][r + 1], p.act);
+            if ((p.dbg & 1) && v0 != 1.2345e30f) continue;
+            if (p.h_half) {
+              store_pair_h(h_zh, m * p.C + c, (m + 1) * p.C + c, v0, v1, ok0, ok1);
+            } else {
+              if (ok0) h_z[m * p.C + c] = v0;
+              if (ok1) h_z[(m + 1) * p.C + c] = v1;
             }
-        }
+          }
       }
     }
     if constexpr (!XEARLY) load_x(bm0 + tile_step);
@@ -759,14 +723,14 @@ int fsv_spade_prep(const float* wg, const float* wb, const float* bg, const floa
   return fsv_check_launch();
 }
 
-static inline int fsv_sp_fill_site(SpadeP& p, int s, int nmaps, const float* const* wg, const float* const* wb,
+static inline int fsv_sp_fill_weights(SpadeP& p, int nmaps, const float* const* wg, const float* const* wb,
                                    const float* const* bg, const float* const* bb, const long long* w_bstride,
                                    const long long* b_bstride) {
   for (int k = 0; k < FSV_SP_MAXMAPS; ++k) {
     const bool on = k < nmaps;
-    p.wg[s][k] = on ? wg[k] : nullptr; p.wb[s][k] = on ? wb[k] : nullptr;
-    p.bg[s][k] = on ? bg[k] : nullptr; p.bb[s][k] = on ? bb[k] : nullptr;
-    p.w_bstride[s][k] = on ? w_bstride[k] : 0; p.b_bstride[s][k] = on ? b_bstride[k] : 0;
+    p.wg[k] = on ? wg[k] : nullptr; p.wb[k] = on ? wb[k] : nullptr;
+    p.bg[k] = on ? bg[k] : nullptr; p.bb[k] = on ? bb[k] : nullptr;
+    p.w_bstride[k] = on ? w_bstride[k] : 0; p.b_bstride[k] = on ? b_bstride[k] : 0;
     if (on && (!wg[k] || !wb[k] || !bg[k] || !bb[k])) return FSV_ERR_UNSUPPORTED;
   }
   return FSV_OK;
@@ -780,13 +744,7 @@ static inline int fsv_sp_fill_common(SpadeP& p, const float* x, const float* mea
   // 32-bit byte offsets inside one sample of a map / inside x (buffer descriptors)
   if ((long long)N * HW * C * 4 > FSV_BUF_MAX_BYTES || (long long)HW * 2 * C * 4 > FSV_BUF_MAX_BYTES) return FSV_ERR_UNSUPPORTED;
   p.x = x; p.mean = mean; p.rstd = rstd; p.nmaps = nmaps;
-  for (int s = 0; s < FSV_SP_SITES; ++s) {
-    p.h[s] = nullptr; p.act[s] = FSV_ACT_NONE;
-    for (int k = 0; k < FSV_SP_MAXMAPS; ++k) {
-      p.wg[s][k] = p.wb[s][k] = p.bg[s][k] = p.bb[s][k] = nullptr;
-      p.w_bstride[s][k] = p.b_bstride[s][k] = 0;
-    }
-  }
+  p.h = nullptr; p.act = FSV_ACT_NONE;
   for (int k = 0; k < FSV_SP_MAXMAPS; ++k) {
     const bool on = k < nmaps;
     p.map[k] = on ? maps[k] : nullptr; p.ch[k] = on ? ch[k] : 0; p.dgb[k] = nullptr;
@@ -799,21 +757,17 @@ static inline int fsv_sp_fill_common(SpadeP& p, const float* x, const float* mea
   p.h_half = 0;
   p.dbsum = nullptr; p.db_slots = 1; p.db_slot_stride = 0;
   for (int k = 0; k < FSV_SP_MAXMAPS; ++k) p.db_zstride[k] = 0;
-  {
-    const char* e = getenv("FSV_SPADE_DBG");
-    p.dbg = e ? atoi(e) : 0;
-  }
+  p.dbg = (int)fsv_env("FSV_SPADE_DBG", 0);
   return FSV_OK;
 }
 
 // pixel-tile workgroups of a launch: as many as stay resident at once (256 CUs x wgs_per_cu), each walking its share of the tiles
 static inline unsigned fsv_sp_grid_x(int ntiles, int gy, int n, int wgs_per_cu) {
-  const char* e = getenv("FSV_SPADE_WGS_PER_CU");           // in-box experiments; 0 = one workgroup per tile
-  if (e) wgs_per_cu = atoi(e);
+  wgs_per_cu = (int)fsv_env("FSV_SPADE_WGS_PER_CU", wgs_per_cu);       // in-box experiments; 0 = one workgroup per tile
   if (wgs_per_cu <= 0) return (unsigned)ntiles;
   long long cap = (256ll * wgs_per_cu) / ((long long)gy * n);
-  const char* m = getenv("FSV_SPADE_MAX_GX");               // tests: a multi-tile walk on a small map
-  if (m && atoi(m) > 0) cap = atoi(m);
+  const int max_gx = (int)fsv_env("FSV_SPADE_MAX_GX", 0);   // tests: a multi-tile walk on a small map
+  if (max_gx > 0) cap = max_gx;
   if (cap < 1) cap = 1;
   return (unsigned)(ntiles < cap ? ntiles : cap);
 }
@@ -828,9 +782,9 @@ static int fsv_spade_mod_fwd_impl(const float* x, const float* mean, const float
   SpadeP p;
   int rc = fsv_sp_fill_common(p, x, mean, rstd, nmaps, maps, ch, N, HW, C, ldw, stat_bstride, W, up);
   if (rc) return rc;
-  rc = fsv_sp_fill_site(p, 0, nmaps, wg, wb, bg, bb, w_bstride, b_bstride);
+  rc = fsv_sp_fill_weights(p, nmaps, wg, wb, bg, bb, w_bstride, b_bstride);
   if (rc) return rc;
-  p.h[0] = h; p.act[0] = act; p.h_half = flags & 1;
+  p.h = h; p.act = act; p.h_half = flags & 1;
   const bool f16 = (flags & 4) != 0;
   if (f16) {            // half maps / half N-major weights: 16-byte vectors of 8 k
     for (int k = 0; k < nmaps; ++k)
@@ -839,13 +793,13 @@ static int fsv_spade_mod_fwd_impl(const float* x, const float* mean, const float
   if (C <= 32) {
     const int gy = fsv_cdiv(C, 32);
     dim3 g(fsv_sp_grid_x(fsv_cdiv(HW, 128), gy, N, 3), gy, N);
-    if (f16) FSV_LAUNCH((fsv_spade_mod_kernel<128, 32, 4, 1, 1, false, true>), g, dim3(256), stream, p);
-    else FSV_LAUNCH((fsv_spade_mod_kernel<128, 32, 4, 1, 1, false>), g, dim3(256), stream, p);
+    if (f16) FSV_LAUNCH((fsv_spade_mod_kernel<128, 32, 4, 1, false, true>), g, dim3(256), stream, p);
+    else FSV_LAUNCH((fsv_spade_mod_kernel<128, 32, 4, 1, false>), g, dim3(256), stream, p);
   } else {
     const int gy = fsv_cdiv(C, 64);
     dim3 g(fsv_sp_grid_x(fsv_cdiv(HW, 64), gy, N, f16 ? 4 : 3), gy, N);
-    if (f16) FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, 1, false, true>), g, dim3(256), stream, p);
-    else FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, 1, false>), g, dim3(256), stream, p);
+    if (f16) FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, false, true>), g, dim3(256), stream, p);
+    else FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, false>), g, dim3(256), stream, p);
   }
   return fsv_check_launch();
 }
@@ -873,34 +827,6 @@ int fsv_spade_mod_fwd_h(const float* x, const float* mean, const float* rstd, vo
                                 w_bstride, b_bstride, N, HW, C, ldw, stat_bstride, act, W, up, flags, stream);
 }
 
-// Two norm sites of one SPADEResnetBlock in ONE launch (architecture.py:95-96,103: bn_0 and bn_s normalise the same x with the
-// same statistics and read the same maps): h0 = act0(SPADE_0(x)), h1 = act1(SPADE_s(x)).  Arrays are [2 * nmaps]: site 0's
-// entries first.
-int fsv_spade_mod_fwd2(const float* x, const float* mean, const float* rstd, float* h0, float* h1,
-                       int nmaps, const float* const* maps, const float* const* wg, const float* const* wb,
-                       const float* const* bg, const float* const* bb, const int* ch, const long long* w_bstride,
-                       const long long* b_bstride, int N, int HW, int C, int ldw, long long stat_bstride, int act0, int act1,
-                       int W, int up, hipStream_t stream) {
-  if (!h0 || !h1 || nmaps < 1) return FSV_ERR_BAD_ARG;
-  SpadeP p;
-  int rc = fsv_sp_fill_common(p, x, mean, rstd, nmaps, maps, ch, N, HW, C, ldw, stat_bstride, W, up);
-  if (rc) return rc;
-  for (int s = 0; s < 2; ++s) {
-    rc = fsv_sp_fill_site(p, s, nmaps, wg + s * nmaps, wb + s * nmaps, bg + s * nmaps, bb + s * nmaps, w_bstride + s * nmaps,
-                          b_bstride + s * nmaps);
-    if (rc) return rc;
-  }
-  p.h[0] = h0; p.h[1] = h1; p.act[0] = act0; p.act[1] = act1;
-  if (C <= 32) {
-    dim3 g(fsv_cdiv(HW, 128), fsv_cdiv(C, 32), N);
-    FSV_LAUNCH((fsv_spade_mod_kernel<128, 32, 4, 1, 2, false>), g, dim3(256), stream, p);
-  } else {
-    dim3 g(fsv_cdiv(HW, 64), fsv_cdiv(C, 64), N);
-    FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, 2, false>), g, dim3(256), stream, p);
-  }
-  return fsv_check_launch();
-}
-
 // Backward twin of fsv_spade_mod_fwd (see the kernel comment): same operands, dh in, dgb[k] ([P][2C] per map) and dxhat out.
 static int fsv_spade_mod_bwd_impl(const float* x, const float* mean, const float* rstd, const float* dh,
                       int nmaps, const float* const* maps, const float* const* wg, const float* const* wb,
@@ -913,9 +839,9 @@ static int fsv_spade_mod_bwd_impl(const float* x, const float* mean, const float
   SpadeP p;
   int rc = fsv_sp_fill_common(p, x, mean, rstd, nmaps, maps, ch, N, HW, C, ldw, stat_bstride, W, up);
   if (rc) return rc;
-  rc = fsv_sp_fill_site(p, 0, nmaps, wg, wb, bg, bb, w_bstride, b_bstride);
+  rc = fsv_sp_fill_weights(p, nmaps, wg, wb, bg, bb, w_bstride, b_bstride);
   if (rc) return rc;
-  p.dh = dh; p.dxhat = dxhat; p.act[0] = act; p.h_half = flags & 3;
+  p.dh = dh; p.dxhat = dxhat; p.act = act; p.h_half = flags & 3;
   const bool f16 = (flags & 4) != 0;
   if (f16) {
     for (int k = 0; k < nmaps; ++k)
@@ -942,11 +868,11 @@ static int fsv_spade_mod_bwd_impl(const float* x, const float* mean, const float
   const int gy = fsv_cdiv(C, 64);
   dim3 g(fsv_sp_grid_x(fsv_cdiv(HW, 64), gy, N, nmaps <= 1 ? 3 : 2), gy, N);
   if (nmaps <= 1) {
-    if (f16) FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, 1, true, true, 1>), g, dim3(256), stream, p);
-    else FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, 1, true, false, 1>), g, dim3(256), stream, p);
+    if (f16) FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, true, true, 1>), g, dim3(256), stream, p);
+    else FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, true, false, 1>), g, dim3(256), stream, p);
   } else {
-    if (f16) FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, 1, true, true>), g, dim3(256), stream, p);
-    else FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, 1, true>), g, dim3(256), stream, p);
+    if (f16) FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, true, true>), g, dim3(256), stream, p);
+    else FSV_LAUNCH((fsv_spade_mod_kernel<64, 64, 2, 2, true>), g, dim3(256), stream, p);
   }
   return fsv_check_launch();
 }

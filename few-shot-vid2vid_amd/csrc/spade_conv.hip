@@ -490,8 +490,8 @@ static int fsv_spade_conv_s_impl(const float* x, const float* mean, const float*
   // as many pixel-tile walkers as stay resident (two workgroups per CU)
   const int ntiles = fsv_cdiv(HW, 64);
   long long cap = (256ll * 2) / N;
-  const char* e = getenv("FSV_SPADE_MAX_GX");               // tests: a multi-tile walk on a small map
-  if (e && atoi(e) > 0) cap = atoi(e);
+  const int max_gx = (int)fsv_env("FSV_SPADE_MAX_GX", 0);   // tests: a multi-tile walk on a small map
+  if (max_gx > 0) cap = max_gx;
   if (cap < 1) cap = 1;
   dim3 g((unsigned)(ntiles < cap ? ntiles : cap), 1, N);
   if (f16) {

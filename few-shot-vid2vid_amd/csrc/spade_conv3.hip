@@ -408,8 +408,8 @@ int fsv_spade_conv3_fwd(const float* x, const float* mean, const float* rstd, fl
   p.tiles_x = fsv_cdiv(W, 16);
   p.ntiles = p.tiles_x * fsv_cdiv(H, 8);
   dim3 g((unsigned)(((p.ntiles + 7) / 8) * 8), 1, N);
-  const char* e = getenv("FSV_S3_RW");                   // in-box A/B: 32-row weight chunks for Cout 32 as well (64: half the
-  const bool rw64 = !(e && atoi(e) == 32);               // barriers, measured 1 - 2.5 % faster)
+  // in-box A/B: 32-row weight chunks for Cout 32 as well (64: half the barriers, measured 1 - 2.5 % faster)
+  const bool rw64 = (int)fsv_env("FSV_S3_RW", 64) != 32;
   if (Cout == 32 && rw64) FSV_LAUNCH((fsv_spade_conv3_kernel<1, 64>), g, dim3(256), stream, p);
   else if (Cout == 32) FSV_LAUNCH((fsv_spade_conv3_kernel<1, 32>), g, dim3(256), stream, p);
   else FSV_LAUNCH((fsv_spade_conv3_kernel<2, 32>), g, dim3(256), stream, p);

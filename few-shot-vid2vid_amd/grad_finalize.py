@@ -81,13 +81,7 @@ class GradFinalizer:
         lib.call("fsv_colsum_grouped", lib.ptr(table), len(jobs), lib.ptr(tmap1), nblk1, lib.ptr(tmap2), nblk2,
                  lib.ptr(part), lib.stream_ptr())
 
-    def zero_arena(self):
-        """the arena's fill ahead of time (FlatAdam.zero_early, on a side stream); begin_pass(prezeroed=True) then skips it unless
-        it has to allocate a larger arena"""
-        if self.arena is not None:
-            self.arena.zero_()
-
-    def begin_pass(self, prezeroed=False):
+    def begin_pass(self):
         """Called by FlatAdam.zero_grad right before a backward pass."""
         self.jobs = []
         self.bias_jobs = []
@@ -95,8 +89,7 @@ class GradFinalizer:
         if self._arena_need and not capturing and (self.arena is None or self.arena.numel() < self._arena_need):
             self.arena = None
             self.arena = torch.empty(self._arena_need, dtype=torch.float32, device=self._arena_dev)
-            prezeroed = False
-        if self.arena is not None and not prezeroed:
+        if self.arena is not None:
             self.arena.zero_()
         self._arena_off = 0
         self._arena_need = 0

@@ -212,7 +212,7 @@ class LayoutCache:
     def refresh_split(self, part, lo, hi):
         """Rewrite the layouts of the weights that lie in bytes [lo, hi) of the optimiser's flat parameter buffer (part 0) or
         outside of it (part 1): an optimiser step issued in two pieces refreshes each piece's layouts behind its own Adam
-        launch (FlatAdam.step_stage2_early).  fp32 layouts only (the caller keeps `--amp` on the one-piece step)."""
+        launch (FlatAdam.adam_part).  fp32 layouts only (the caller keeps `--amp` on the one-piece step)."""
         if not self.entries:
             return
         key = (lo, hi)

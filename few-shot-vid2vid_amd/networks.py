@@ -109,30 +109,12 @@ class BatchNorm(nn.Module):
         if self.training:
             self._pending += 1
 
-    # Two forward passes of ONE network issued next to each other on different streams (model.Vid2VidModel's twin generator passes)
-    # must not both read-modify-write the running statistics.  While `_redirect` is set, a module found in it hands its kernels a
-    # ZEROED stand-in pair instead: the kernel's update `r = (1 - m) r + m s` leaves exactly `m s` there, and the caller folds it
-    # into the real buffers in pass order afterwards (`running = (1 - m) running + stand-in`: the same two products and one sum as
-    # the in-place update, bit for bit).  A module may be met once per redirected pass (its second update would need (1 - m)^2).
-    _redirect = None
     MOMENTUM = 0.1
-
-    def buffers(self):
-        red = BatchNorm._redirect
-        if red is not None and self.training:
-            hit = red.get(id(self))
-            if hit is not None:
-                if hit[2]:
-                    raise RuntimeError("a BatchNorm site was met twice in a redirected pass")
-                hit[2] = True
-                return hit[0], hit[1]
-        return self.running_mean, self.running_var
 
     def forward(self, x, act=ACT_NONE):
         self.note_forward()
-        rm, rv = self.buffers()
         return ops.norm_act(x, self.weight if self.affine else None, self.bias if self.affine else None,
-                            rm, rv, instance=False, eps=1e-5, momentum=BatchNorm.MOMENTUM, act=act,
+                            self.running_mean, self.running_var, instance=False, eps=1e-5, momentum=BatchNorm.MOMENTUM, act=act,
                             training=self.training)
 
 
@@ -213,8 +195,7 @@ class SPADE(nn.Module):
                 use_w.append((wg, wb, zb, zb))
             use_maps.append(m)
         self.norm.note_forward()
-        rm, rv = self.norm.buffers()
-        return ops.spade_mod(x, use_maps, use_w, rm, rv, act=act, training=self.training, up=up)
+        return ops.spade_mod(x, use_maps, use_w, self.norm.running_mean, self.norm.running_var, act=act, training=self.training, up=up)
 
 
 class AdaptiveConv2d(nn.Module):
@@ -276,25 +257,17 @@ class SPADEResnetBlock(nn.Module):
         if up and not fold:
             x = ops.upsample2x(x)
         if self.spade:
-            # the fused SPADE launches (two-site, bn_s -> conv_s, actvn(bn) -> conv3x3) are 1x1-only: a 3x3 SPADE (--spade_ks 3) declines
+            # the fused SPADE launches (bn_s -> conv_s, actvn(bn) -> conv3x3) are 1x1-only: a 3x3 SPADE (--spade_ks 3) declines
             # them here and runs as its own launch (csrc/spade_k3.hip) followed by the gather-GEMM convolution
             k1 = self.spade_ks == 1
-            conv3 = k1 and ops.spade_conv3_enabled() and not ops.spade_pair_enabled()      # (two opt-ins that both want bn_0: the pair wins)
+            conv3 = k1 and ops.spade_conv3_enabled()
             if self.learned_shortcut:
-                # bn_s and bn_0 normalise the same x with the same maps: one two-site launch (ops.spade_pair)
-                if k1 and ops.spade_pair_enabled():
-                    with ops.spade_pair():
-                        hs = self.bn_s(x, label, nw[2], act=ACT_NONE, up=fold)
-                        h0 = self.bn_0(x, label, nw[0], act=ACT_LRELU, up=fold)
-                    x_s = self._conv('conv_s', hs, cw[2])
-                else:
-                    # bn_s -> conv_s as ONE kernel where csrc/spade_conv.hip covers the widths (ops.spade_into_conv)
-                    with (ops.spade_into_conv() if k1 else contextlib.nullcontext()):
-                        x_s = self._conv('conv_s', self.bn_s(x, label, nw[2], act=ACT_NONE, up=fold), cw[2])
-                    h0 = None if conv3 else self.bn_0(x, label, nw[0], act=ACT_LRELU, up=fold)
+                # bn_s -> conv_s as ONE kernel where csrc/spade_conv.hip covers the widths (ops.spade_into_conv)
+                with (ops.spade_into_conv() if k1 else contextlib.nullcontext()):
+                    x_s = self._conv('conv_s', self.bn_s(x, label, nw[2], act=ACT_NONE, up=fold), cw[2])
             else:
                 x_s = x
-                h0 = None if conv3 else self.bn_0(x, label, nw[0], act=ACT_LRELU, up=fold)
+            h0 = None if conv3 else self.bn_0(x, label, nw[0], act=ACT_LRELU, up=fold)
             # conv_0 feeds bn_1, conv_1 (+ shortcut) the next block's bn_0 / bn_s: BatchNorm statistics from their epilogues
             # (in training mode only: eval-mode BatchNorm takes its running buffers and would leave the partials unused; a next
             # block that materialises the up-sampling - up and not fold - reduces over the up-sampled tensor itself)
@@ -758,11 +731,6 @@ class FewShotGenerator(nn.Module):
         for a, l in zip(fi, fl):
             b, c, h, w = a.shape
             sm = ops.softmax_channels(l)
-            if ops.pooled_product_ready(a, sm):
-                # round 6, opt-in (FSV_POOL_WGRAD=1, measured neutral): the product over positions as a per-sample 1x1 weight-gradient
-                # GEMM - both operands read in place
-                enc.append(ops.pooled_product(a, sm))                               # [b, c(i), c(j), 1]
-                continue
             # prod[b, i, j] = sum_p a[b, i, p] * sm[b, j, p]  as a per-sample 1x1 "convolution" on the gather-GEMM
             # kernel: pixels = image channels i, input channels = positions p, generated weights = softmax rows j
             a_rows = a.reshape(b, c, 1, h * w).permute(0, 3, 1, 2)              # logical [b, hw, c, 1]
@@ -892,30 +860,13 @@ class FewShotGenerator(nn.Module):
             self._sn_count = sum(1 for _ in self.modules())
         self._sn_group.update(self.training)
 
-    def begin_pass(self):
-        """One power iteration of every spectral layer NOW, for a forward pass that is issued later (possibly on another stream,
-        possibly behind further begin_pass() calls): the (layer, sigma / u / v snapshot) list is queued and the next forward pass
-        takes it instead of iterating itself - the iterations keep their order whatever the order the passes run in."""
-        self._sn_update()
-        snap = [(l, l._sig_cached) for l in self._sn_group.layers]
-        for l, _ in snap:
-            l._sig_cached = None
-        if getattr(self, '_sn_presets', None) is None:
-            self._sn_presets = []
-        self._sn_presets.append(snap)
-
     def forward(self, label, label_refs, img_refs, prev=(None, None), t=0, img_coarse=None):
         from .conv import stats_pass
         with stats_pass(label.device):          # a no-op inside Vid2VidModel.forward's pass; opens one for bare generator calls
             return self._forward(label, label_refs, img_refs, prev, t, img_coarse)
 
     def _forward(self, label, label_refs, img_refs, prev=(None, None), t=0, img_coarse=None):
-        presets = getattr(self, '_sn_presets', None)
-        if presets:
-            for l, c in presets.pop(0):          # this pass's power iteration was issued ahead of it (begin_pass)
-                l._sig_cached = c
-        else:
-            self._sn_update()
+        self._sn_update()
         if img_coarse is not None:
             return self.forward_face(label, label_refs, img_refs, img_coarse)
         if self.n_shot == 1 and label_refs.shape[1] == 1:

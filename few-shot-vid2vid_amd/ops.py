@@ -909,60 +909,6 @@ def mlp_bank(rows, chains):
     return list(_MlpBankFn.apply(meta, *flat))
 
 
-class _PooledFn(torch.autograd.Function):
-    """prod[b, i, j] = sum_p a[b, i, p] * sm[b, j, p]: the softmax pooling of the reference encoder (generator.py:378-389,
-    `torch.bmm(x, softmax(label).transpose)`), a and sm NCHW tensors in channels-last memory.
-
-    Both operands lie in memory as [position p][channel]: the product over positions is exactly the shape of a per-sample 1x1
-    WEIGHT-GRADIENT GEMM, `dwt[ci][co] = sum_pixels in[pixel][ci] * dout[pixel][co]`, whose kernel reads both of them in place
-    (round 6; before: a transposed copy of each operand + a K-major re-arrangement + a gather-GEMM whose "pixels" were the 32 ...
-    1024 channels - four launches per level and pass, 17 - 26 us for the GEMM alone on the 16x16 maps).  One launch, one split
-    (direct stores, fixed summation order).  Backward in the operands' own layouts as well: d a[p][i] = sum_j sm[p][j] dprod[i][j] and
-    d sm[p][j] = sum_i a[p][i] dprod[i][j] are per-sample 1x1 convolutions over the positions whose K-major weight operands are
-    dprod re-arranged (a c x c matrix) and dprod itself."""
-
-    @staticmethod
-    def forward(ctx, a, sm):
-        a_, sm_ = to_nhwc(a), to_nhwc(sm)
-        b, c, h, w = a_.shape
-        g1 = Geom(1, 1, 1, 0)
-        dwt = conv_wgrad(a_, sm_, g1, (c, c, 1, 1), per_sample=True, raw=True, force_split=1)       # [b, c, c] (c % 32 == 0)
-        ctx.save_for_backward(a_, sm_)
-        return dwt.view(b, c, c, 1)
-
-    @staticmethod
-    def backward(ctx, dprod):
-        a_, sm_ = ctx.saved_tensors
-        b, c, h, w = a_.shape
-        g1 = Geom(1, 1, 1, 0)
-        d = dprod.reshape(b, c, c).contiguous()
-        da = dsm = None
-        if ctx.needs_input_grad[0]:
-            wt, _, ldw = prep_weight(d.view(b, c, c, 1, 1), 0, g1)            # K-major [j][i] per sample
-            da = conv_forward(sm_, wt, ldw, c, g1, per_sample=True)
-        if ctx.needs_input_grad[1]:
-            dsm = conv_forward(a_, d, c, c, g1, per_sample=True)              # K-major [i][j] = dprod as it lies in memory
-        return da, dsm
-
-
-def pooled_product_ready(a, sm):
-    """can _PooledFn take this pair?  (channel counts a multiple of 32: no padding rows / columns in the c x c results; the float4
-    weight-gradient kernel's geometry; the exact-fp32 kernels.)  Opt-in, FSV_POOL_WGRAD=1: measured in-box against the gather-GEMM
-    form over three alternating pairs - 42.49 / 42.42 / 42.46 ms per step with the gather-GEMM, 42.48 / 42.59 / 42.55 with this one
-    (profiles/r06_notes.md section 9): the ~40 launches it removes sit on the reference-encoder chain, which runs next to the flow
-    branch and is not what the step waits for."""
-    if a.shape != sm.shape or a.dim() != 4 or a.dtype != torch.float32 or sm.dtype != torch.float32:
-        return False
-    b, c, h, w = a.shape
-    return (c % 32 == 0 and 32 // w + 1 <= h and _conv.narrow_staging_mode() == 0 and
-            _os.environ.get('FSV_POOL_WGRAD', '0') == '1')
-
-
-def pooled_product(a, sm):
-    """[b, c(i), c(j), 1] = sum over positions of a[b, i, p] * sm[b, j, p] (see _PooledFn)"""
-    return _PooledFn.apply(a, sm)
-
-
 def batch_conv(x, weight, bias=None, act=ACT_NONE, stride=1, allow_half=True, res=None):
     """Per-sample 1x1 (or kxk) convolution with generated weights [B, Cout, Cin, k, k] (base_network.py:56-71);
     stride 1 or 2 (padding k // 2, as the reference).  allow_half=False: a call site that only borrows the kernel for a
@@ -1094,30 +1040,6 @@ def norm_act(x, weight=None, bias=None, run_mean=None, run_var=None, instance=Fa
 _spade_tls = _threading.local()
 
 
-class spade_pair:
-    """`with spade_pair():` around the two SPADE sites of one SPADEResnetBlock that normalise the SAME tensor with the same
-    maps (bn_s and bn_0, architecture.py:95-96,103): the first site's modulation launch is held back and issued together with
-    the second one's as ONE two-site launch (csrc/spade.hip NS = 2: x, the statistics and the label-map tiles are read once).
-    Nobody may read the first site's output before the block ends.  Autograd is untouched (two nodes, two backward twins).
-    Opt-in (FSV_SPADE_PAIR=1): measured in-box in round 3 (profiles/r03_notes.md) the two-site launch is no faster than the two
-    single-site launches (51.64 vs 51.45 ms per step) - its 80 KB of LDS and 206 registers leave one or two workgroups per CU, and
-    the reads it saves (x at a quarter of the resolution, the 32-channel maps) are L2 hits for the second single-site launch
-    anyway."""
-
-    def __enter__(self):
-        self.pending = None
-        self.outer = getattr(_spade_tls, 'pair', None)
-        _spade_tls.pair = self if _os.environ.get('FSV_SPADE_PAIR', '0') == '1' else None
-        return self
-
-    def __exit__(self, et, ev, tb):
-        _spade_tls.pair = self.outer
-        if self.pending is not None and et is None:
-            site, self.pending = self.pending, None
-            _spade_launch(site)
-        return False
-
-
 class spade_into_conv:
     """`with spade_into_conv():` around `x_s = conv_s(bn_s(x, maps))` of a SPADEResnetBlock (architecture.py:103-108): the
     modulation launch of bn_s is held back, and the 1x1 convolution that consumes its output issues BOTH as one kernel
@@ -1150,10 +1072,6 @@ class spade_into_conv:
             site, self.pending = self.pending, None
             _spade_launch(site)
         return False
-
-
-def spade_pair_enabled():
-    return _os.environ.get('FSV_SPADE_PAIR', '0') == '1'
 
 
 def spade_conv3_enabled():
@@ -1280,11 +1198,6 @@ def _spade_conv3_launch(site, wt, ldwc, cout, wscale, bias, res, want_hs, st=Non
     return out
 
 
-def _spade_same_input(a, b):
-    return (a['x'].data_ptr() == b['x'].data_ptr() and a['dims'] == b['dims'] and a['chs'] == b['chs'] and
-            [m.data_ptr() for m in a['maps']] == [m.data_ptr() for m in b['maps']])
-
-
 def _half_map(key, m):
     """IEEE-half copy of a label map (NHWC), made once per map tensor: every SPADE site of a block and their backward twins and
     weight-gradient GEMMs read the same copy"""
@@ -1299,35 +1212,23 @@ def _half_map(key, m):
     return mh
 
 
-def _spade_launch(a, b=None):
+def _spade_launch(a):
     arr = lambda v: (ctypes.c_void_p * max(len(v), 1))(*v)
     n, hw, c, ldw, w, up = a['dims']
     chs = a['chs']
-    if b is None:
-        with profile.scope('fsv_spade_mod_kernel' + (' P%d C%d K%s' % (n * hw, c, '+'.join(map(str, chs))) if profile.detail() else ''),
-                           a['flops']):
-            if a.get('half'):
-                lib.call("fsv_spade_mod_fwd_h", lib.ptr(a['x']), lib.ptr(a['mean']), lib.ptr(a['rstd']), lib.ptr(a['h']), len(chs),
-                         _pp(a['maps']), arr(a['wg']), arr(a['wb']), arr(a['bg']), arr(a['bb']), lib.int_array(chs + [0]),
-                         _ll(a['wstr'] + [0]), _ll(a['bstr'] + [0]), n, hw, c, ldw, 0, a['act'], w, up,
-                         1 | (4 if a.get('f16') else 0), lib.stream_ptr())
-                if _hconv.launch_hook() is not None:
-                    _hconv.launch_hook()('spade_fwd', dict(site=a))
-            else:
-                lib.call("fsv_spade_mod_fwd", lib.ptr(a['x']), lib.ptr(a['mean']), lib.ptr(a['rstd']), lib.ptr(a['h']), len(chs),
-                         _pp(a['maps']), arr(a['wg']), arr(a['wb']), arr(a['bg']), arr(a['bb']), lib.int_array(chs + [0]),
-                         _ll(a['wstr'] + [0]), _ll(a['bstr'] + [0]), n, hw, c, ldw, 0, a['act'], w, up, lib.stream_ptr())
-        return
-    with profile.scope('fsv_spade_mod_kernel', a['flops'] + b['flops']):
-        lib.call("fsv_spade_mod_fwd2", lib.ptr(a['x']), lib.ptr(a['mean']), lib.ptr(a['rstd']), lib.ptr(a['h']), lib.ptr(b['h']),
-                 len(chs), _pp(a['maps']), arr(a['wg'] + b['wg']), arr(a['wb'] + b['wb']), arr(a['bg'] + b['bg']),
-                 arr(a['bb'] + b['bb']), lib.int_array(chs + [0]), _ll(a['wstr'] + b['wstr'] + [0]),
-                 _ll(a['bstr'] + b['bstr'] + [0]), n, hw, c, ldw, 0, a['act'], b['act'], w, up, lib.stream_ptr())
-
-
-def _streams_mod():
-    from . import streams
-    return streams
+    with profile.scope('fsv_spade_mod_kernel' + (' P%d C%d K%s' % (n * hw, c, '+'.join(map(str, chs))) if profile.detail() else ''),
+                       a['flops']):
+        if a.get('half'):
+            lib.call("fsv_spade_mod_fwd_h", lib.ptr(a['x']), lib.ptr(a['mean']), lib.ptr(a['rstd']), lib.ptr(a['h']), len(chs),
+                     _pp(a['maps']), arr(a['wg']), arr(a['wb']), arr(a['bg']), arr(a['bb']), lib.int_array(chs + [0]),
+                     _ll(a['wstr'] + [0]), _ll(a['bstr'] + [0]), n, hw, c, ldw, 0, a['act'], w, up,
+                     1 | (4 if a.get('f16') else 0), lib.stream_ptr())
+            if _hconv.launch_hook() is not None:
+                _hconv.launch_hook()('spade_fwd', dict(site=a))
+        else:
+            lib.call("fsv_spade_mod_fwd", lib.ptr(a['x']), lib.ptr(a['mean']), lib.ptr(a['rstd']), lib.ptr(a['h']), len(chs),
+                     _pp(a['maps']), arr(a['wg']), arr(a['wb']), arr(a['bg']), arr(a['bb']), lib.int_array(chs + [0]),
+                     _ll(a['wstr'] + [0]), _ll(a['bstr'] + [0]), n, hw, c, ldw, 0, a['act'], w, up, lib.stream_ptr())
 
 
 class _SpadeFn(torch.autograd.Function):
@@ -1380,8 +1281,7 @@ class _SpadeFn(torch.autograd.Function):
         # a SPADEResnetBlock, architecture.py:92-99) that would round it to half anyway - the kernel rounds at the store and the
         # fp32 tensor + conversion pass disappear; its gradient then arrives as half (the convolutions' data gradient) and the
         # backward twin reads it as such
-        ctx.half_out = bool(_conv.h_kernels() and ctx.fast and _os.environ.get('FSV_SPADE_FUSED_BWD', '1') == '1'
-                            and getattr(_spade_tls, 'pair', None) is None and nmaps > 0)
+        ctx.half_out = bool(_conv.h_kernels() and ctx.fast and _os.environ.get('FSV_SPADE_FUSED_BWD', '1') == '1' and nmaps > 0)
         hout = _hconv.empty_nhwc_h(n, c, h, w, x) if ctx.half_out else empty_nhwc(n, c, h, w, x)
         # ... and the gamma / beta GEMMs themselves on the f16 matrix instructions: half label maps (one conversion per map tensor,
         # shared by every SPADE site that reads it and by the backward), half weights, half d(gamma|beta) for the half data /
@@ -1420,12 +1320,6 @@ class _SpadeFn(torch.autograd.Function):
                     hit = getattr(wgs[k], '_fsv_spade_prep', None)
                     if hit is not None and hit[0] == key:
                         wcat_x, wcat_d, bcat = hit[1]
-                        if len(hit) > 2 and hit[2] is not None and x.is_cuda:
-                            cur_s = torch.cuda.current_stream(x.device)
-                            if cur_s != hit[3]:          # built by the other of two passes issued next to each other (streams.CROSS)
-                                cur_s.wait_event(hit[2])
-                                for t_ in hit[1]:
-                                    t_.record_stream(cur_s)
                         prepped += [wcat_x, wcat_d, bcat]
                         if ctx.f16:
                             wg_p.append(wcat_x.data_ptr()); wb_p.append(wcat_x.data_ptr() + 2 * c * kt)
@@ -1461,36 +1355,21 @@ class _SpadeFn(torch.autograd.Function):
                     wg_p.append(wcat_t.data_ptr()); wb_p.append(wcat_t.data_ptr() + 4 * c)
                     wstr.append(kt * 2 * c if per_sample else 0)
                 if owner is not None:
-                    ev_ = st_ = None
-                    if _streams_mod().CROSS and x.is_cuda:
-                        st_ = torch.cuda.current_stream(x.device)
-                        ev_ = torch.cuda.Event()
-                        ev_.record(st_)
-                    wgs[k]._fsv_spade_prep = (key, tuple(prepped[-3:]), ev_, st_)
+                    wgs[k]._fsv_spade_prep = (key, tuple(prepped[-3:]))
                 bg_p.append(bcat.data_ptr()); bb_p.append(bcat.data_ptr() + 4 * c)
                 bstr.append(2 * c if per_sample else 0)
             site = dict(x=x, mean=mean, rstd=rstd, h=hout, maps=maps, wg=wg_p, wb=wb_p, bg=bg_p, bb=bb_p, chs=chs, wstr=wstr,
                         bstr=bstr, dims=(n, h * w, c, ldw, w, up), act=act, keep=prepped, half=ctx.half_out, f16=ctx.f16,
                         flops=2.0 * n * h * w * c * 2 * sum(chs))
-            pair = getattr(_spade_tls, 'pair', None)
             defer = getattr(_spade_tls, 'defer', None)
             conv3 = bool(defer is not None and defer.conv3)
-            if (defer is not None and defer.pending is None and pair is None and nmaps > 0 and
+            if (defer is not None and defer.pending is None and nmaps > 0 and
                     ((not conv3 and (ctx.f16 or not ctx.half_out) and act == ACT_NONE and c in (64, 128)) or
                      (conv3 and not ctx.half_out and act in (ACT_NONE, ACT_LRELU) and c == 64))):
                 site['conv3'] = conv3
                 defer.pending = site            # the convolution that reads hout issues both (spade_into_conv)
-            elif pair is None or nmaps == 0:
-                _spade_launch(site)
-            elif pair.pending is None:
-                pair.pending = site             # the partner site of this block issues both (spade_pair)
             else:
-                first, pair.pending = pair.pending, None
-                if _spade_same_input(first, site):
-                    _spade_launch(first, site)
-                else:
-                    _spade_launch(first)
-                    _spade_launch(site)
+                _spade_launch(site)
             ctx.nmaps, ctx.act = nmaps, act
             ctx.batch_stats = bool(training or run_mean is None)
             ctx.world = bn_sync_world(1) if ctx.batch_stats else 1
@@ -1522,7 +1401,7 @@ class _SpadeFn(torch.autograd.Function):
     def _forward_k3(ctx, act, up, training, run_mean, x, mean, rstd, maps, wgs, wbs, bgs, bbs, n, c, h, w):
         """--spade_ks 3 (normalization.py:18-52 with ks = 3): ONE launch of csrc/spade_k3.hip (the 3x3 gamma / beta GEMMs on the fp32
         matrix cores, the modulation of every map and the activation in its epilogue).  The 1x1-only fusions decline it on purpose:
-        no site is handed to spade_into_conv (bn_s -> conv_s, FSV_SPADE_CONV3) or spade_pair (FSV_SPADE_PAIR), there is no f16 form
+        no site is handed to spade_into_conv (bn_s -> conv_s, FSV_SPADE_CONV3), there is no f16 form
         (networks.FewShotGenerator refuses --amp with spade_ks 3), and the operands are prepared on every call (no
         FSV_SPADE_PREP_CACHE entry that a replayed graph could leave stale).  A forward that keeps a graph also writes gamma | beta
         ([P][2C] per map): the backward runs the element-wise chain fsv_spade_bwd_elem on it instead of recomputing the 9 * Ch-deep
@@ -2011,7 +1890,7 @@ class _L1Fn(torch.autograd.Function):
         loss = torch.empty(1, dtype=torch.float32, device=a.device)
         lib.check_device(a, bt, mt)
         lib.call("fsv_l1_fwd", lib.ptr(a), lib.ptr(bt), bconst, lib.ptr(mt), dims[0], dims[1], dims[2], _ll(sa_), _ll(sb_),
-                 lib.ptr(part), lib.ptr(loss), _loss_ticket(a), lib.stream_ptr())
+                 lib.ptr(part), lib.ptr(loss), lib.stream_ptr())
         ctx.meta = (dims, sa_, sb_, bconst, bt is not None, mt is not None)
         ctx.save_for_backward(a, bt if bt is not None else a, mt if mt is not None else a)
         return loss
@@ -2035,18 +1914,6 @@ def l1_loss(a, b, mask=None):
 
 
 _wvec_cache = {}
-
-
-def _loss_ticket(like):
-    """the ticket of a loss reduction that finishes in its own launch (csrc/losses.hip fsv_loss_finish; round 6: a dozen 5-us
-    finishing launches per step at the serial point between the forward and the backward pass).  None: the two-launch form - the
-    default.  Opt-in (FSV_LOSS_TICKET=1): bit-identical, and measured SLOWER in-box, 42.41 / 42.52 / 42.53 ms per step without,
-    42.92 / 42.87 / 42.85 with (profiles/r06_step_ab_serial_point.txt) - every workgroup of the fourteen launches pays a
-    device-scope release (an L2 write-back on this part) in front of its ticket, which costs more than the 5-us launches it saves
-    (the round-3 and round-5 findings about producer-side tickets, once more)."""
-    if _os.environ.get('FSV_LOSS_TICKET', '0') != '1':
-        return None
-    return _conv.ticket_range(like, 64)
 
 
 class _WsumFn(torch.autograd.Function):
@@ -2105,7 +1972,7 @@ class _HingeFn(torch.autograd.Function):
         part = torch.empty(512, dtype=torch.float64, device=x.device)
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         lib.check_device(x)
-        lib.call("fsv_hinge_fwd", lib.ptr(x), x.numel(), float(sign), lib.ptr(part), lib.ptr(loss), _loss_ticket(x), lib.stream_ptr())
+        lib.call("fsv_hinge_fwd", lib.ptr(x), x.numel(), float(sign), lib.ptr(part), lib.ptr(loss), lib.stream_ptr())
         ctx.sign = float(sign)
         ctx.save_for_backward(x)
         return loss

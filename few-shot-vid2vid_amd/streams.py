@@ -61,37 +61,6 @@ def shared(make):
     return t
 
 
-CROSS = False       # set while two passes of one iteration are issued on different streams: values one pass caches for the
-                    # other (model._memoised, ops._SpadeFn's fixed-weight operands) then carry an event
-
-FORK_ROOT = None    # set by a caller that issues a pass on a SIDE stream (model.Vid2VidModel's twin generator passes): the branches
-                    # of a fork inside that pass then start from this stream - the capture's origin - instead of the side stream.
-                    # hipStreamEndCapture of ROCm 7.2 crashes on a branch of a branch (round 6: segmentation fault in capture_end,
-                    # gone with the inner fork off); a sibling of the side stream is fine.  Only valid while the side stream has
-                    # launched nothing since it was forked from FORK_ROOT that the branches read (the caller's responsibility).
-
-_held = None        # while a `hold()` block is open: side streams that forks inside it took (they stay reserved until it closes)
-
-
-class hold:
-    """`with hold():` - the side streams that forks inside the block take stay reserved until the block closes.  A forward pass that
-    is issued on one stream while ANOTHER pass of the same shape is issued next to it (model.Vid2VidModel's twin generator passes)
-    must not hand its branch streams to that pass: the second pass's branches would queue behind the first's on the device."""
-
-    def __enter__(self):
-        global _held
-        self.prev, _held = _held, []
-        return self
-
-    def __exit__(self, *exc):
-        global _held
-        for s in _held:
-            if any(s is b for b in _busy):
-                _busy.remove(s)
-        _held = self.prev
-        return False
-
-
 def fork(ref, fns):
     """[f() for f in fns]; on a GPU fns[1:] run on side streams next to fns[0] on the current one and are joined before the
     return.  `ref` is any tensor of the pass (it names the device; CPU / emulated tensors run the branches in order)."""
@@ -103,16 +72,13 @@ def fork(ref, fns):
     _busy.extend(sides)
     try:
         for s, i in zip(sides, range(1, len(fns))):
-            s.wait_stream(cur if FORK_ROOT is None else FORK_ROOT)
+            s.wait_stream(cur)
             with torch.cuda.stream(s):
                 outs[i] = fns[i]()
         outs[0] = fns[0]()
     finally:
         for s in sides:
-            if _held is not None:
-                _held.append(s)          # stays in _busy until the enclosing hold() closes
-            else:
-                _busy.remove(s)
+            _busy.remove(s)
     for s, i in zip(sides, range(1, len(fns))):
         cur.wait_stream(s)
         _record(outs[i], cur)

@@ -266,15 +266,6 @@ int fsv_spade_mod_fwd_h(const float* x, const float* mean, const float* rstd, vo
 /* wcat_h [B][2C][Kh = ceil32(Ch)] halves, K contiguous, zero padded: rows [0, C) gamma weights, [C, 2C) beta weights */
 int fsv_spade_prep_h(const float* wg, const float* wb, long long swg, long long swb, void* wcat_h, int B, int C, int Ch,
                      fsv_stream_t stream);
-/* Two norm sites of one SPADEResnetBlock in one launch - bn_0 and bn_s (architecture.py:95-96,103) normalise the same x
- * with the same statistics and read the same maps; only the gamma / beta weights and the activation differ:
- * h0 = act0(SPADE_0(x)), h1 = act1(SPADE_s(x)).  x, the statistics and the label-map tiles are read once, the map tile in LDS
- * feeds four GEMMs.  wg / wb / bg / bb / w_bstride / b_bstride hold 2 * nmaps entries, site 0's first. */
-int fsv_spade_mod_fwd2(const float* x, const float* mean, const float* rstd, float* h0, float* h1,
-                       int nmaps, const float* const* maps, const float* const* wg, const float* const* wb,
-                       const float* const* bg, const float* const* bb, const int* ch, const long long* w_bstride,
-                       const long long* b_bstride, int N, int HW, int C, int ldw, long long stat_bstride, int act0, int act1,
-                       int W, int up, fsv_stream_t stream);
 /* ---- bn_s modulation fused with conv_s (csrc/spade_conv.hip) - replaces `x_s = self.conv_s(self.bn_s(x, ...))`,
  * architecture.py:103-108 (SPADE.forward normalization.py:37-52 followed by the bias-free spectral-norm 1x1 convolution) ------
  * ONE launch: the gamma / beta GEMMs run with swapped operands (accumulators = [channel][pixel]), the modulated values are the A
@@ -511,12 +502,8 @@ int fsv_adam_step_range(float* param, const float* grad, float* m, float* v, flo
 
 /* ---- losses, D-input packing, mask pooling (csrc/losses.hip) - models/networks/loss.py:69-83,130-138;
  * models/loss_collector.py:47-58,105-110,180; models/input_process.py:59 -------------------------------------------- */
-/* ticket (nullable, fsv_l1_fwd / fsv_hinge_fwd): ONE zeroed int owned by this launch until it completes - the workgroup that takes
- * the last ticket sums the per-workgroup partials in index order (the bits of the two-launch form) and leaves the int at zero;
- * NULL: a second launch finishes the reduction */
 int fsv_l1_fwd(const float* a, const float* b, float bconst, const float* m, int N, int C, long long P,
-               const long long* a_strides, const long long* b_strides, double* part, float* loss, int* ticket,
-               fsv_stream_t stream);
+               const long long* a_strides, const long long* b_strides, double* part, float* loss, fsv_stream_t stream);
 int fsv_l1_bwd(const float* a, const float* b, float bconst, const float* m, int N, int C, long long P,
                const long long* a_strides, const long long* b_strides, const float* gloss, float* da, float* db, float* dm,
                fsv_stream_t stream);
@@ -525,7 +512,7 @@ int fsv_l1_bwd(const float* a, const float* b, float bconst, const float* m, int
  * array of device pointers, weights: n host floats - both travel in the kernel argument); dterms[i] = weights[i] * g[0] */
 int fsv_wsum_fwd(const float* const* terms, const float* weights, int n, float* out, fsv_stream_t stream);
 int fsv_wsum_bwd(const float* weights, int n, const float* g, float* dterms, fsv_stream_t stream);
-int fsv_hinge_fwd(const float* x, long long n, float sign, double* part, float* loss, int* ticket, fsv_stream_t stream);
+int fsv_hinge_fwd(const float* x, long long n, float sign, double* part, float* loss, fsv_stream_t stream);
 int fsv_hinge_bwd(const float* x, long long n, float sign, const float* gloss, float* dx, fsv_stream_t stream);
 int fsv_pack_d_input(const float* ref, const float* lab, const float* fake, const float* real, float* out,
                      int B, int Cr, int Cl, int Ci, long long P, const long long* ref_strides, const long long* lab_strides,

@@ -1221,57 +1221,6 @@ def check_conv_groups(device, seed=77, big=False):
         assert_close('grouped wgrad vs single %s' % (shp,), got, one, tol=2e-6)
 
 
-def check_spade_pair(device, n=2, c=64, chs=(16, 8, 8), h=10, w=12, up=True, seed=55):
-    """Two SPADE sites on the same x and maps (bn_s / bn_0 of a SPADEResnetBlock) through ops.spade_pair - ONE two-site launch -
-    against the same two sites launched one by one: outputs bit-equal (same arithmetic per element), gradients equal (the
-    backward passes are the single-site twins either way).  The single-site form is held to the oracle by check_spade."""
-    ops, conv = pkg()
-    g = torch.Generator().manual_seed(seed)
-    xs_h, xs_w = (h // 2, w // 2) if up else (h, w)
-    x = torch.randn(n, c, xs_h, xs_w, generator=g)
-    maps = [torch.randn(n, ch, h, w, generator=g) for ch in chs]
-
-    def site_weights(gen0):
-        ws = []
-        for k, ch in enumerate(chs):
-            if k == 0 and gen0:
-                ws.append((torch.randn(n, c, ch, 1, 1, generator=g) * 0.3, torch.randn(n, c, ch, 1, 1, generator=g) * 0.3,
-                           torch.randn(n, c, generator=g) * 0.3, torch.randn(n, c, generator=g) * 0.3))
-            else:
-                ws.append((torch.randn(c, ch, 1, 1, generator=g) * 0.3, torch.randn(c, ch, 1, 1, generator=g) * 0.3,
-                           torch.randn(c, generator=g) * 0.3, torch.randn(c, generator=g) * 0.3))
-        return ws
-    w_s, w_0 = site_weights(True), site_weights(True)
-    dy_s, dy_0 = torch.randn(n, c, h, w, generator=g), torch.randn(n, c, h, w, generator=g)
-
-    def run(paired):
-        # channels-last tensors, as between the layers of the network: both sites then see the SAME x / map buffers
-        cl = lambda t: _dev(t, device).contiguous(memory_format=torch.channels_last)
-        xd = cl(x).requires_grad_(True)
-        md = [cl(m).requires_grad_(True) for m in maps]
-        wd_s = [tuple(_dev(t, device).requires_grad_(True) for t in ws) for ws in w_s]
-        wd_0 = [tuple(_dev(t, device).requires_grad_(True) for t in ws) for ws in w_0]
-        rm = [_dev(torch.zeros(c), device) for _ in range(2)]
-        rv = [_dev(torch.ones(c), device) for _ in range(2)]
-        import contextlib, os
-        os.environ['FSV_SPADE_PAIR'] = '1'            # opt-in switch of the two-site launch
-        with (ops.spade_pair() if paired else contextlib.nullcontext()):
-            hs = ops.spade_mod(xd, md, wd_s, rm[0], rv[0], act=conv.ACT_NONE, up=up)
-            h0 = ops.spade_mod(xd, md, wd_0, rm[1], rv[1], act=conv.ACT_LRELU, up=up)
-        os.environ.pop('FSV_SPADE_PAIR', None)
-        ((hs * _dev(dy_s, device)).sum() + (h0 * _dev(dy_0, device)).sum()).backward()
-        grads = [xd.grad] + [m.grad for m in md] + [t.grad for ws in wd_s + wd_0 for t in ws]
-        return hs.detach(), h0.detach(), grads, rm, rv
-    hs1, h01, g1, rm1, rv1 = run(False)
-    hs2, h02, g2, rm2, rv2 = run(True)
-    assert float((hs1.cpu() - hs2.cpu()).abs().max()) == 0.0 and float((h01.cpu() - h02.cpu()).abs().max()) == 0.0, \
-        'two-site launch differs from the single-site launches'
-    for i, (a, b) in enumerate(zip(g1, g2)):
-        assert_close('paired spade grad %d' % i, b, a, tol=1e-6)
-    for a, b in zip(rm1 + rv1, rm2 + rv2):
-        assert float((a.cpu() - b.cpu()).abs().max()) == 0.0
-
-
 def check_spade_conv_s(device, n=2, c=64, cout=32, chs=(16, 8), h=10, w=12, up=True, grad=True, spectral=True, seed=57,
                        max_gx=None, amp=False):
     """x_s = conv_s(bn_s(x, maps)) (architecture.py:103-108) through ops.spade_into_conv - ONE launch of csrc/spade_conv.hip -
@@ -1508,54 +1457,6 @@ def check_spade_conv3(device, n=2, c=64, cout=32, chs=(16, 8), h=20, w=24, up=Tr
             assert_close('fused bn -> actvn -> conv3x3 grad %d vs the oracle' % i, b, a, tol=4e-5)
 
 
-def check_pooled_product(device, b=2, c=64, h=16, w=16, seed=97):
-    """ops.pooled_product: prod[b, i, j] = sum_p a[b, i, p] * softmax(l)[b, j, p] (generator.py:378-389: torch.bmm of the image
-    features with the transposed channel softmax of the label features) issued as a per-sample 1x1 weight-gradient GEMM (round 6:
-    both operands read in place) - values and both gradients against the bmm, and against the gather-GEMM form it replaces
-    (the default, FSV_POOL_WGRAD=0) at summation-order distance; the launch list: one weight-gradient launch, no re-arrangement, no copy."""
-    from importlib import import_module
-    ops, conv = pkg()
-    lib = import_module('few-shot-vid2vid_amd.lib')
-    networks = import_module('few-shot-vid2vid_amd.networks')
-    g = torch.Generator().manual_seed(seed)
-    a0 = torch.randn(b, c, h, w, generator=g)
-    l0 = torch.randn(b, c, h, w, generator=g)
-    dy = torch.randn(b, c, c, 1, generator=g)
-
-    def run(new):
-        cl = lambda t: _dev(t, device).detach().clone().contiguous(memory_format=torch.channels_last).requires_grad_(True)
-        a, l = cl(a0), cl(l0)
-        seen, real_call = [], lib.call
-
-        def recording_call(name, *args):
-            seen.append(name)
-            return real_call(name, *args)
-        os.environ['FSV_POOL_WGRAD'] = '1' if new else '0'
-        lib.call = recording_call
-        try:
-            (enc,) = networks.FewShotGenerator._pooled([a], [l])
-            n_fwd = len(seen)
-            (enc * _dev(dy, device)).sum().backward()
-        finally:
-            lib.call = real_call
-            os.environ.pop('FSV_POOL_WGRAD', None)
-        return enc.detach(), a.grad, l.grad, seen[:n_fwd], seen[n_fwd:]
-    y1, ga1, gl1, f1, b1 = run(True)
-    y0, ga0, gl0, f0, b0 = run(False)
-    assert f1 == ['fsv_softmax_rows_fwd', 'fsv_conv_wgrad'], f1
-    assert 'fsv_conv_wgrad' not in f0 and len(f0) > len(f1), f0
-    # backward: two position-major 1x1 convolutions + one c x c re-arrangement; no weight-gradient launch, no un-arrangement
-    assert [n for n in b1 if n != 'fsv_conv_plan'] == ['fsv_prep_weight', 'fsv_conv_gather_fwd', 'fsv_conv_gather_fwd', 'fsv_softmax_rows_bwd'], b1
-    ar, lr = a0.clone().requires_grad_(True), l0.clone().requires_grad_(True)
-    sm = torch.softmax(lr, dim=1)
-    ref = torch.bmm(ar.reshape(b, c, h * w), sm.reshape(b, c, h * w).transpose(1, 2)).unsqueeze(-1)
-    (ref * dy).sum().backward()
-    for nm, got, want in (('product', y1, ref), ('d a', ga1, ar.grad), ('d label', gl1, lr.grad),
-                          ('product vs the gather-GEMM form', y1, y0), ('d a vs the gather-GEMM form', ga1, ga0),
-                          ('d label vs the gather-GEMM form', gl1, gl0)):
-        assert_close('softmax pooling ' + nm, got, want, tol=2e-5)
-
-
 def check_weighted_sum(device, seed=96):
     """ops.weighted_sum (the loss collector's `sum(lambda_i * term_i)`, loss_collector.py:60-67,161-162,204,218-219) as one launch
     each way (round 6) against the torch expression: value to the last fp32 rounding of a sequential sum, every term's gradient
@@ -1586,35 +1487,25 @@ def check_weighted_sum(device, seed=96):
                 assert float(t.grad.cpu()) == float(want) == float(t0.grad.cpu()), (i, t.grad, want, t0.grad)
 
 
-def check_loss_ticket(device, seed=95):
-    """The loss reductions that finish in their own launch (csrc/losses.hip fsv_loss_finish, round 6: the last workgroup sums the
-    partials in index order) give the BITS of the two-launch form (FSV_LOSS_TICKET=0), for several grid sizes, repeatedly (the
-    ticket must come back to zero), and issue one launch instead of two."""
-    from importlib import import_module
+def check_loss_reductions(device, seed=95):
+    """The two-launch loss reductions (csrc/losses.hip: per-workgroup partials, then fsv_loss_final_kernel sums them in index order):
+    L1, masked L1, masked L1 against a constant and both hinge losses against torch for several grid sizes, each three times over
+    with the same bits."""
     ops, conv = pkg()
-    lib = import_module('few-shot-vid2vid_amd.lib')
     g = torch.Generator().manual_seed(seed)
     for shape in ((1, 3, 5, 7), (2, 8, 33, 40), (2, 3, 128, 160)):
         a, b = _dev(torch.randn(*shape, generator=g), device), _dev(torch.randn(*shape, generator=g), device)
         m = _dev((torch.rand(shape[0], 1, *shape[2:], generator=g) > 0.4).float(), device)
         x = _dev(torch.randn(*shape, generator=g), device)
-        got = {}
-        for mode in ('1', '0'):
-            os.environ['FSV_LOSS_TICKET'] = mode
-            seen, real_call = [], lib.call
-            lib.call = lambda name, *args: (seen.append(name), real_call(name, *args))[1]
-            try:
-                vals = []
-                for _ in range(3):
-                    vals += [ops.l1_loss(a, b), ops.l1_loss(a, b, m), ops.l1_loss(a, 1.0, m), ops.hinge_loss(x, True),
-                             ops.hinge_loss(x, False)]
-                got[mode] = torch.cat([v.detach().reshape(1).cpu() for v in vals])
-            finally:
-                lib.call = real_call
-                os.environ.pop('FSV_LOSS_TICKET', None)
-        assert torch.equal(got['1'], got['0']), (got['1'], got['0'])
-        ref = torch.stack([(a - b).abs().mean().cpu(), ((a - b) * m).abs().mean().cpu()])
-        assert float((got['1'][:2] - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
+        vals = []
+        for _ in range(3):
+            vals += [ops.l1_loss(a, b), ops.l1_loss(a, b, m), ops.l1_loss(a, 1.0, m), ops.hinge_loss(x, True),
+                     ops.hinge_loss(x, False)]
+        got = torch.cat([v.detach().reshape(1).cpu() for v in vals])
+        assert torch.equal(got[:5], got[5:10]) and torch.equal(got[:5], got[10:])
+        ref = torch.stack([(a - b).abs().mean().cpu(), ((a - b) * m).abs().mean().cpu(), ((a - 1.0) * m).abs().mean().cpu(),
+                           -torch.clamp(x - 1, max=0).mean().cpu(), -torch.clamp(-x - 1, max=0).mean().cpu()])
+        assert float((got[:5] - ref).abs().max()) <= 1e-5 * float(ref.abs().max()), (got[:5], ref)
 
 
 def check_conv_stats(device, seed=61):
@@ -1726,13 +1617,4 @@ def _check_thin_conv(device, ops, conv, g):
         thin = conv.conv_forward(xn, wf, ldw, cout, ge, bias=_dev(b, device))
         mfma = conv.conv_forward(xn, wf, ldw, cout, ge, bias=_dev(b, device), force_tile=4, force_split=1)
         assert_close(name + ': vector-ALU kernel vs the gather-GEMM kernel (summation order)', thin, mfma, tol=2e-6)
-        if k == 3:
-            # round 6 (opt-in, measured neutral): the 3x3 form keeps the lane's weights in registers and issues its nine tap loads
-            # together - the same fma chain per output as the generic tap loop, bit for bit
-            os.environ['FSV_THIN_T9'] = '1'
-            try:
-                t9 = conv.conv_forward(xn, wf, ldw, cout, ge, bias=_dev(b, device))
-            finally:
-                os.environ.pop('FSV_THIN_T9', None)
-            assert bool((thin == t9).all()), name + ': register-resident 3x3 form changed the bits'
 

@@ -130,7 +130,7 @@ def test_conv_params_free_block_against_torch(emu_lib):
 
 
 def test_fused_spade_launches_decline_a_per_sample_convolution(emu_lib, monkeypatch):
-    """bn_s -> conv_s (on by default), FSV_SPADE_CONV3 and FSV_SPADE_PAIR are written for shared convolution weights: with every
+    """bn_s -> conv_s (on by default) and FSV_SPADE_CONV3 are written for shared convolution weights: with every
     switch on, a conv_params_free block launches the held-back modulations on their own and gives the same output as with the
     switches off"""
     from importlib import import_module
@@ -141,7 +141,7 @@ def test_fused_spade_launches_decline_a_per_sample_convolution(emu_lib, monkeypa
     label = torch.randn(2, 8, 8, 8, generator=g)
     outs = []
     for on in ('0', '1'):
-        for k in ('FSV_SPADE_CONV_S', 'FSV_SPADE_CONV3', 'FSV_SPADE_PAIR'):
+        for k in ('FSV_SPADE_CONV_S', 'FSV_SPADE_CONV3'):
             monkeypatch.setenv(k, on)
         seen, real = [], lib.call
         monkeypatch.setattr(lib, 'call', lambda name, *a: (seen.append(name), real(name, *a))[1])

@@ -189,17 +189,7 @@ def test_spade_modulation_fused_with_the_3x3_convolution(emu_lib):
 
 def test_weighted_sum_of_loss_terms(emu_lib):
     oc.check_weighted_sum(DEV)
-    oc.check_loss_ticket(DEV)
-
-
-def test_softmax_pooling_as_a_weight_gradient_gemm(emu_lib):
-    oc.check_pooled_product(DEV)
-    oc.check_pooled_product(DEV, b=1, c=32, h=8, w=16, seed=98)
-
-
-def test_spade_two_site_launch(emu_lib):
-    oc.check_spade_pair(DEV)
-    oc.check_spade_pair(DEV, c=32, chs=(8,), h=9, w=7, up=False)
+    oc.check_loss_reductions(DEV)
 
 
 def test_norm_statistics_from_the_conv_epilogue(emu_lib):

@@ -196,18 +196,7 @@ def test_spade_modulation_fused_with_the_3x3_convolution(hip_lib):
 
 def test_weighted_sum_of_loss_terms(hip_lib):
     oc.check_weighted_sum(dev())
-    oc.check_loss_ticket(dev())
-
-
-def test_softmax_pooling_as_a_weight_gradient_gemm(hip_lib):
-    oc.check_pooled_product(dev())
-    oc.check_pooled_product(dev(), b=1, c=32, h=8, w=16, seed=98)
-    oc.check_pooled_product(dev(), b=2, c=1024, h=16, w=16, seed=99)
-
-
-def test_spade_two_site_launch(hip_lib):
-    oc.check_spade_pair(dev())
-    oc.check_spade_pair(dev(), c=32, chs=(8,), h=9, w=7, up=False)
+    oc.check_loss_reductions(dev())
 
 
 def test_norm_statistics_from_the_conv_epilogue(hip_lib):

@@ -65,7 +65,7 @@ def test_options_that_still_raise(kw, word):
 
 
 def test_fused_spade_launches_decline_a_3x3_spade(emu_lib, monkeypatch):
-    """bn_s -> conv_s (on by default), FSV_SPADE_CONV3 and FSV_SPADE_PAIR are 1x1-only: with every switch on, a 3x3 SPADE block runs
+    """bn_s -> conv_s (on by default) and FSV_SPADE_CONV3 are 1x1-only: with every switch on, a 3x3 SPADE block runs
     the 3x3 modulation kernel and plain convolutions, and gives the same output as with the switches off"""
     from importlib import import_module
     net, lib = mc._net(), import_module('few-shot-vid2vid_amd.lib')
@@ -76,7 +76,7 @@ def test_fused_spade_launches_decline_a_3x3_spade(emu_lib, monkeypatch):
     blk0 = net.SPADEResnetBlock(64, 32, hidden_nc=8, spade=True, spade_ks=3)
     outs = []
     for on in ('0', '1'):
-        for k in ('FSV_SPADE_CONV_S', 'FSV_SPADE_CONV3', 'FSV_SPADE_PAIR'):
+        for k in ('FSV_SPADE_CONV_S', 'FSV_SPADE_CONV3'):
             monkeypatch.setenv(k, on)
         seen, real = [], lib.call
         monkeypatch.setattr(lib, 'call', lambda name, *a: (seen.append(name), real(name, *a))[1])
