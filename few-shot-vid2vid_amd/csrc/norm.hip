@@ -6,18 +6,21 @@
 //   * InstanceNorm2d(affine=True, eps=0.1) of the discriminator: normalization.py:82
 // A tensor is viewed as [G groups][P pixels][C channels]: BatchNorm has G = 1, P = N*H*W; InstanceNorm has
 // G = N, P = H*W.  Reductions are two-stage and deterministic: per-block partial sums (fp32 within a thread's
-// short run, fp64 across threads and blocks) followed by a one-block-per-channel-slab finalize.
+// short run, fp64 across threads and blocks; the cross-replica sums of fsv_norm_sums are fp64 from the first addition)
+// followed by a one-block-per-channel-slab finalize.
 #include "fsv_common.h"
+#include <type_traits>
 
 // ---- two-value column reductions over [G][P][C] -------------------------------------------------------------
-// One template serves the three reductions of this file:
+// One template serves the four reductions of this file:
 //   STATS  : (sum x, sum x^2)                           forward statistics
+//   STATS64: the same with fp64 accumulators in the thread and in LDS (fsv_norm_sums: sums that leave the device)
 //   BWD    : (sum d, sum d * xhat), d = dy * act'(y)     normalisation backward
 //   COLSUM : (sum x, -)                                  bias gradients
 // Grid = (pixel chunks, channel slabs, groups).  A block covers TX column units (float4 = 4 channels when
 // C % 4 == 0) x TY = 256/TX rows in flight; every thread keeps 4 independent row streams so that >= 4 vector loads
-// per input are outstanding (these kernels are pure HBM streams).  Per-thread fp32 partials over a short run are
-// combined in fp64 across the block and written as part[g][chunk][c][2]; a finalize kernel sums the chunks.
+// per input are outstanding (these kernels are pure HBM streams).  Per-thread partials over a short run (fp32; fp64 in
+// STATS64) are combined in fp64 across the block and written as part[g][chunk][c][2]; a finalize kernel sums the chunks.
 struct RedPlan { int V, CU, TX, TY, nslabs, rows_per_blk, nchunks; };
 
 static inline RedPlan fsv_red_plan(int G, int P, int C, int max_chunks = 0) {
@@ -41,6 +44,10 @@ static inline RedPlan fsv_red_plan(int G, int P, int C, int max_chunks = 0) {
 #define FSV_RED_STATS 0
 #define FSV_RED_BWD 1
 #define FSV_RED_COLSUM 2
+// STATS with fp64 accumulators from the first addition on (products exact): the sums that leave the device for the cross-replica
+// exchange (fsv_norm_sums).  E[x^2] - mean^2 then only loses what the fp32 DATA lost - a channel at 100 +- 0.01 keeps its
+// variance, which fp32 products (one ulp of 1e4 is ten times that variance) do not.
+#define FSV_RED_STATS64 3
 
 __device__ __forceinline__ float fsv_act_grad(float dy, float y, int act) {
   if (act == FSV_ACT_LRELU) return y > 0.f ? dy : 0.2f * dy;
@@ -72,7 +79,9 @@ __device__ __forceinline__ void fsv_sum_chunks(const double* part, int g, int c,
 
 template <int MODE, int V>
 __global__ __launch_bounds__(256) void fsv_red2_kernel(RedP p) {
-  __shared__ float red[256 * 2 * V];
+  constexpr bool WIDE = MODE == FSV_RED_STATS64;
+  typedef typename std::conditional<WIDE, double, float>::type acc_t;
+  __shared__ acc_t red[256 * 2 * V];
   const int chunk = blockIdx.x, slab = blockIdx.y, g = blockIdx.z;
   const int tx = threadIdx.x % p.TX, ty = threadIdx.x / p.TX;
   const int cu = slab * p.TX + tx;
@@ -80,9 +89,10 @@ __global__ __launch_bounds__(256) void fsv_red2_kernel(RedP p) {
   const int r0 = chunk * p.rows_per_blk;
   const int r1 = (r0 + p.rows_per_blk < p.P) ? r0 + p.rows_per_blk : p.P;
   const long long goff = (long long)g * p.P * p.C;
-  float s1[V], s2[V], mu[V], rs[V];
+  acc_t s1[V], s2[V];
+  float mu[V], rs[V];
 #pragma unroll
-  for (int j = 0; j < V; ++j) { s1[j] = 0.f; s2[j] = 0.f; mu[j] = 0.f; rs[j] = 1.f; }
+  for (int j = 0; j < V; ++j) { s1[j] = 0; s2[j] = 0; mu[j] = 0.f; rs[j] = 1.f; }
   if (active) {
     const int c0 = cu * V;
     if (MODE == FSV_RED_BWD) {
@@ -119,6 +129,7 @@ __global__ __launch_bounds__(256) void fsv_red2_kernel(RedP p) {
 #pragma unroll
         for (int j = 0; j < V; ++j) {
           if (MODE == FSV_RED_STATS) { s1[j] += va[u][j]; s2[j] += va[u][j] * va[u][j]; }
+          else if (WIDE) { const acc_t w = va[u][j]; s1[j] += w; s2[j] += w * w; }
           else if (MODE == FSV_RED_COLSUM) { s1[j] += va[u][j]; }
           else {
             float d = fsv_act_grad(va[u][j], vy[u][j], p.act);
@@ -724,7 +735,7 @@ int fsv_norm_sums(const float* x, double* workspace, double* sums, int P, int C,
   RedPlan pl = fsv_red_plan(1, P, C);
   RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.part = workspace;
   rp.P = P; rp.C = C; rp.act = 0; fsv_red_no_tail(rp);
-  fsv_launch_red<FSV_RED_STATS>(pl, rp, 1, stream);
+  fsv_launch_red<FSV_RED_STATS64>(pl, rp, 1, stream);
   FSV_LAUNCH(fsv_sums_final_kernel, dim3(fsv_cdiv(C, 4)), dim3(256), stream, (const double*)workspace, sums, C, pl.nchunks);
   return fsv_check_launch();
 }

@@ -1,0 +1,80 @@
+"""The optimiser, loss-scale, cross-replica BatchNorm, max-pool and table-helper entry points on a real MI355X against fp64
+PyTorch on the CPU (tests/small_op_checks.py): the checks of tests/test_small_ops_emu.py, same shapes, same bounds."""
+import pytest
+import torch
+
+import small_op_checks as sc
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+
+
+@pytest.mark.parametrize("gscale", sc.ADAM_GSCALES)
+@pytest.mark.parametrize("betas", sc.ADAM_BETAS)
+def test_adam_against_fp64(hip_lib, betas, gscale):
+    sc.check_adam_fp64(DEV, betas, gscale)
+
+
+def test_adam_step_in_ranges(hip_lib):
+    sc.check_adam_ranges(DEV)
+
+
+def test_amp_adam(hip_lib):
+    sc.check_amp_adam(DEV)
+
+
+@pytest.mark.parametrize("n", sc.AMP_CHECK_SIZES)
+def test_amp_check(hip_lib, n):
+    sc.check_amp_check(DEV, n)
+
+
+def test_amp_update(hip_lib):
+    sc.check_amp_update(DEV)
+
+
+@pytest.mark.parametrize("act", ['none', 'lrelu'])
+@pytest.mark.parametrize("world", [1, 2, 3])
+@pytest.mark.parametrize("shape", sc.SYNC_BN_SHAPES)
+def test_sync_bn(hip_lib, shape, world, act):
+    sc.check_sync_bn(DEV, shape[0], shape[1], world, act)
+
+
+def test_sync_bn_cancellation(hip_lib):
+    sc.check_sync_bn_cancellation(DEV)
+
+
+@pytest.mark.parametrize("shape", sc.MAXPOOL_SHAPES)
+def test_maxpool2(hip_lib, shape):
+    sc.check_maxpool2(DEV, shape)
+
+
+@pytest.mark.parametrize("count", [4, 1028, 70000, 1027, 70001])      # the last two end in the scalar tail of a block
+@pytest.mark.parametrize("nsrc", [1, 2, 3, 4])
+def test_sum_terms_one_job(hip_lib, nsrc, count):
+    sc.check_sum_terms(DEV, [nsrc], [count])
+
+
+def test_sum_terms_eight_jobs(hip_lib):
+    sc.check_sum_terms(DEV, [1, 2, 3, 4, 4, 3, 2, 1], [4, 1028, 70000, 4, 1028, 70000, 1028, 4])
+    sc.check_sum_terms(DEV, [4, 3, 2, 1, 1, 2, 3, 4], [70001, 1027, 5, 1028, 70001, 1027, 6, 7])
+
+
+@pytest.mark.parametrize("sizes", [(1,), (4095,), (4096,), (4097,), (20000,), (1, 4095, 4096, 4097, 20000)])
+def test_gather_add(hip_lib, sizes):
+    sc.check_gather_add(DEV, sizes)
+
+
+def test_upload_i64(hip_lib):
+    per_launch = sc.upload_words_per_launch()
+    for n in (1, 7, 64, per_launch, per_launch + 1, 2 * per_launch + 104):
+        sc.check_upload_i64(DEV, n)
+
+
+@pytest.mark.parametrize("shape", [(1000, 7), (300, 260)])
+def test_two_launch_reductions(hip_lib, shape):
+    sc.check_two_launch_reductions(DEV, shape[0], shape[1])
+
+
+@pytest.mark.parametrize("total", sc.ACT_SIZES)
+def test_act_fwd(hip_lib, total):
+    sc.check_act_fwd(DEV, total)
