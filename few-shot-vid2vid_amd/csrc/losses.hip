@@ -1,7 +1,8 @@
 // Loss reductions, discriminator-input packing and label-mask pooling of the G/D step (SURVEY.md section 8a rows
 // a-10 and a-13) - all HBM-bound, all fused into single passes.
 //
-// Reference: models/networks/loss.py:69-83 (hinge), :130-138 (MaskedL1Loss), torch.nn.L1Loss at
+// Reference: models/networks/loss.py:17-104 (GANLoss: hinge :69-79, ls :57-61, original :50-53, w :85-90), :130-138
+// (MaskedL1Loss), torch.nn.L1Loss at
 // models/loss_collector.py:36,152,156,206-215; D input concatenation loss_collector.py:47-58,105-110;
 // MaxPool2d(15)/AvgPool2d(15) masks input_process.py:59, loss_collector.py:180.
 #include "fsv_common.h"
@@ -95,6 +96,45 @@ __global__ __launch_bounds__(256) void fsv_hinge_bwd_kernel(const float* x, long
     float v = sign * x[i] - 1.f;
     dx[i] = v < 0.f ? g : (v == 0.f ? 0.5f * g : 0.f);
   }
+}
+
+// ---- the other GANLoss objectives (--gan_mode ls / original / w), t = 1 for a real target and 0 for a fake one --------------------
+// ls:       (x - t)^2                              d/dx = 2 (x - t)
+// original: max(x, 0) - x t + log1p(exp(-|x|))     d/dx = sigmoid(x) - t     (binary_cross_entropy_with_logits; exp never sees a
+//                                                                            positive argument, so |x| ~ 100 stays finite)
+// w:        -sign * x                              d/dx = -sign              (the backward pass does not read x)
+template <int MODE>
+__device__ __forceinline__ float fsv_gan_term(float x, float t, float sign) {
+  if (MODE == FSV_GAN_LS) { const float d = x - t; return d * d; }
+  if (MODE == FSV_GAN_ORIGINAL) return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+  return -sign * x;
+}
+
+template <int MODE>
+__device__ __forceinline__ float fsv_gan_dterm(float x, float t) {
+  if (MODE == FSV_GAN_LS) return 2.f * (x - t);
+  const float e = expf(-fabsf(x));                       // sigmoid(x) = 1 / (1 + e) for x >= 0, e / (1 + e) below
+  return (x >= 0.f ? 1.f : e) / (1.f + e) - t;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void fsv_gan_fwd_kernel(const float* x, long long n, float sign, double* part) {
+  __shared__ double red[256];
+  const float t = sign > 0.f ? 1.f : 0.f;
+  double acc = 0.0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    acc += (double)fsv_gan_term<MODE>(x[i], t, sign);
+  double s = fsv_block_sum(acc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// loss = (1/n) sum term(x_i)  ->  dx_i = g * term'(x_i) / n
+template <int MODE>
+__global__ __launch_bounds__(256) void fsv_gan_bwd_kernel(const float* x, long long n, float sign, const float* gptr, float* dx) {
+  const float t = sign > 0.f ? 1.f : 0.f;
+  const float g = gptr[0] / (float)n;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    dx[i] = MODE == FSV_GAN_W ? -sign * g : g * fsv_gan_dterm<MODE>(x[i], t);
 }
 
 // ---- discriminator input: out[2B][H][W][Cr + Cl + Ci] (NHWC) = [ref | label | (fake for n < B, real otherwise)] -------------
@@ -290,18 +330,27 @@ int fsv_l1_bwd(const float* a, const float* b, float bconst, const float* m, int
   return fsv_check_launch();
 }
 
-// loss[0] = -(1/n) * sum min(sign * x - 1, 0)
-int fsv_hinge_fwd(const float* x, long long n, float sign, double* part, float* loss, hipStream_t stream) {
-  if (!x || !part || !loss || n < 1) return FSV_ERR_BAD_ARG;
+// the GANLoss reduction, mode = enum fsv_gan_mode.  hinge: loss[0] = -(1/n) * sum min(sign * x - 1, 0); the other objectives:
+// loss[0] = (1/n) * sum term(x) (fsv_gan_term)
+int fsv_hinge_fwd(const float* x, long long n, float sign, int mode, double* part, float* loss, hipStream_t stream) {
+  if (!x || !part || !loss || n < 1 || mode < FSV_GAN_HINGE || mode > FSV_GAN_W) return FSV_ERR_BAD_ARG;
   const int grid = fsv_loss_grid(n);
-  FSV_LAUNCH(fsv_hinge_fwd_kernel, dim3(grid), dim3(256), stream, x, n, sign, part);
-  FSV_LAUNCH(fsv_loss_final_kernel, dim3(1), dim3(256), stream, (const double*)part, grid, loss, -1.0 / (double)n);
+  if (mode == FSV_GAN_HINGE) FSV_LAUNCH(fsv_hinge_fwd_kernel, dim3(grid), dim3(256), stream, x, n, sign, part);
+  else if (mode == FSV_GAN_LS) FSV_LAUNCH(fsv_gan_fwd_kernel<FSV_GAN_LS>, dim3(grid), dim3(256), stream, x, n, sign, part);
+  else if (mode == FSV_GAN_ORIGINAL) FSV_LAUNCH(fsv_gan_fwd_kernel<FSV_GAN_ORIGINAL>, dim3(grid), dim3(256), stream, x, n, sign, part);
+  else FSV_LAUNCH(fsv_gan_fwd_kernel<FSV_GAN_W>, dim3(grid), dim3(256), stream, x, n, sign, part);
+  FSV_LAUNCH(fsv_loss_final_kernel, dim3(1), dim3(256), stream, (const double*)part, grid, loss,
+             (mode == FSV_GAN_HINGE ? -1.0 : 1.0) / (double)n);
   return fsv_check_launch();
 }
 
-int fsv_hinge_bwd(const float* x, long long n, float sign, const float* gloss, float* dx, hipStream_t stream) {
-  if (!x || !gloss || !dx || n < 1) return FSV_ERR_BAD_ARG;
-  FSV_LAUNCH(fsv_hinge_bwd_kernel, dim3(fsv_loss_grid(n)), dim3(256), stream, x, n, sign, gloss, dx);
+int fsv_hinge_bwd(const float* x, long long n, float sign, int mode, const float* gloss, float* dx, hipStream_t stream) {
+  if (!x || !gloss || !dx || n < 1 || mode < FSV_GAN_HINGE || mode > FSV_GAN_W) return FSV_ERR_BAD_ARG;
+  const int grid = fsv_loss_grid(n);
+  if (mode == FSV_GAN_HINGE) FSV_LAUNCH(fsv_hinge_bwd_kernel, dim3(grid), dim3(256), stream, x, n, sign, gloss, dx);
+  else if (mode == FSV_GAN_LS) FSV_LAUNCH(fsv_gan_bwd_kernel<FSV_GAN_LS>, dim3(grid), dim3(256), stream, x, n, sign, gloss, dx);
+  else if (mode == FSV_GAN_ORIGINAL) FSV_LAUNCH(fsv_gan_bwd_kernel<FSV_GAN_ORIGINAL>, dim3(grid), dim3(256), stream, x, n, sign, gloss, dx);
+  else FSV_LAUNCH(fsv_gan_bwd_kernel<FSV_GAN_W>, dim3(grid), dim3(256), stream, x, n, sign, gloss, dx);
   return fsv_check_launch();
 }
 

@@ -136,10 +136,11 @@ def masked_l1(inp, target, mask):
     return ops.l1_loss(inp, target, mask)
 
 
-def gan_loss(preds, real):
-    """GANLoss.__call__ with the hinge objective on a list-of-lists prediction (loss.py:69-79, 92-104): last
-    feature of every scale; the reference calls it with for_discriminator=True in both steps."""
-    return ops.weighted_sum([ops.hinge_loss(p[-1], real) for p in preds], [1.0 / len(preds)] * len(preds))
+def gan_loss(preds, real, mode='hinge'):
+    """GANLoss.__call__ with the --gan_mode objective (hinge / ls / original / w) on a list-of-lists prediction
+    (loss.py:49-90, 92-104): last feature of every scale, mean over the scales; the reference calls it with
+    for_discriminator=True in both steps (an argument only the hinge objective reads)."""
+    return ops.weighted_sum([ops.gan_loss(p[-1], real, mode) for p in preds], [1.0 / len(preds)] * len(preds))
 
 
 _ZEROS = {}
@@ -151,6 +152,11 @@ class LossCollector:
 
     def __init__(self, opt):
         self.opt = opt
+        self.gan_mode = getattr(opt, 'gan_mode', 'hinge')            # loss_collector.py:35 GANLoss(opt.gan_mode, ...)
+        ops.gan_mode_code(self.gan_mode)                             # ValueError on anything but hinge / ls / original / w
+        if self.gan_mode != 'hinge' and amp_mode(opt) != conv.MFMA_F32:
+            raise NotImplementedError("gan_mode = %r under --amp (the half-precision step is built for the hinge objective only)"
+                                      % (self.gan_mode,))
         self.pose = 'pose' in opt.dataset_mode
         self.has_fg = self.pose
         self.warp_ref = opt.warp_ref
@@ -230,14 +236,14 @@ class LossCollector:
             pred_fake = [[t[:half] for t in scale] for scale in out]
             pred_real = [[t[half:] for t in scale] for scale in out]
         if for_discriminator:
-            return [gan_loss(pred_real, True), gan_loss(pred_fake, False)]
+            return [gan_loss(pred_real, True, self.gan_mode), gan_loss(pred_fake, False, self.gan_mode)]
         terms = []
         if not self.opt.no_ganFeat_loss:
             for sf, sr in zip(pred_fake, pred_real):
                 for a, b in zip(sf[:-1], sr[:-1]):
                     terms.append(l1(a, b.detach()))
         feat = ops.weighted_sum(terms, [self.opt.lambda_feat / len(pred_fake)] * len(terms)) if terms else self.zero(fake)
-        return [gan_loss(pred_fake, True), feat]
+        return [gan_loss(pred_fake, True, self.gan_mode), feat]
 
     def crop_face_region(self, image, label):
         """face_refiner.py:32-39: device-side boxes + one crop/resize launch (csrc/face.hip)."""

@@ -1963,17 +1963,31 @@ def weighted_sum(terms, weights=None):
     return cat.sum(dim=0, keepdim=True)
 
 
+GAN_MODES = {'hinge': lib.ENUMS['FSV_GAN_HINGE'], 'ls': lib.ENUMS['FSV_GAN_LS'], 'original': lib.ENUMS['FSV_GAN_ORIGINAL'],
+             'w': lib.ENUMS['FSV_GAN_W']}
+
+
+def gan_mode_code(mode):
+    """--gan_mode string -> enum fsv_gan_mode of include/fsv2v.h; anything else raises like GANLoss.__init__ (loss.py:28-37)"""
+    if mode not in GAN_MODES:
+        raise ValueError('Unexpected gan_mode {}'.format(mode))
+    return GAN_MODES[mode]
+
+
 class _HingeFn(torch.autograd.Function):
-    """-mean(min(sign * x - 1, 0))  (GANLoss hinge, models/networks/loss.py:69-79): sign = +1 real, -1 fake."""
+    """GANLoss.loss (models/networks/loss.py:49-90) of one prediction map, sign = +1 real (t = 1), -1 fake (t = 0); mode = enum
+    fsv_gan_mode: hinge -mean(min(sign * x - 1, 0)) (:69-79), ls mean((x - t)^2) (:57-61), original BCE-with-logits (:50-53),
+    w -sign * mean(x) (:85-90)."""
 
     @staticmethod
-    def forward(ctx, x, sign):
+    def forward(ctx, x, sign, mode=0):
         x = x if (x.is_contiguous() or (x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous())) else x.contiguous()
         part = torch.empty(512, dtype=torch.float64, device=x.device)
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         lib.check_device(x)
-        lib.call("fsv_hinge_fwd", lib.ptr(x), x.numel(), float(sign), lib.ptr(part), lib.ptr(loss), lib.stream_ptr())
+        lib.call("fsv_hinge_fwd", lib.ptr(x), x.numel(), float(sign), int(mode), lib.ptr(part), lib.ptr(loss), lib.stream_ptr())
         ctx.sign = float(sign)
+        ctx.mode = int(mode)
         ctx.save_for_backward(x)
         return loss
 
@@ -1981,12 +1995,17 @@ class _HingeFn(torch.autograd.Function):
     def backward(ctx, g):
         (x,) = ctx.saved_tensors
         dx = torch.empty_like(x)
-        lib.call("fsv_hinge_bwd", lib.ptr(x), x.numel(), ctx.sign, lib.ptr(g.contiguous()), lib.ptr(dx), lib.stream_ptr())
-        return dx, None
+        lib.call("fsv_hinge_bwd", lib.ptr(x), x.numel(), ctx.sign, ctx.mode, lib.ptr(g.contiguous()), lib.ptr(dx), lib.stream_ptr())
+        return dx, None, None
+
+
+def gan_loss(x, real, mode='hinge'):
+    """the --gan_mode objective of one discriminator prediction map -> shape [1] (csrc/losses.hip fsv_hinge_fwd / _bwd)"""
+    return _HingeFn.apply(x, 1.0 if real else -1.0, gan_mode_code(mode))
 
 
 def hinge_loss(x, real):
-    return _HingeFn.apply(x, 1.0 if real else -1.0)
+    return gan_loss(x, real, 'hinge')
 
 
 class _PackDFn(torch.autograd.Function):

@@ -35,6 +35,9 @@ enum fsv_act { FSV_ACT_NONE = 0, FSV_ACT_LRELU = 1 /* leaky_relu(0.2), architect
                /* gather-GEMM epilogue only: out = v * leaky_relu'(res) (res = the activated output of the layer below): the
                 * activation-backward pass of a Linear + LeakyReLU chain (generator.py:103-110) folded into the data gradient */
                FSV_ACT_DLRELU = 6 };
+/* objective of fsv_hinge_fwd / fsv_hinge_bwd: the reference's --gan_mode (GANLoss, models/networks/loss.py:17-104) */
+enum fsv_gan_mode { FSV_GAN_HINGE = 0 /* loss.py:69-79 */, FSV_GAN_LS = 1 /* :57-61 */, FSV_GAN_ORIGINAL = 2 /* :50-53 */,
+                    FSV_GAN_W = 3 /* :85-90 */ };
 
 /* ---- convolution family (csrc/conv_igemm.hip) -----------------------------------------------------------------
  * Replaces F.conv2d at architecture.py:22-27,60,81-84; generator.py:112-131,479-504,541-572;
@@ -500,7 +503,7 @@ int fsv_adam_step(float* param, const float* grad, float* m, float* v, float* st
 int fsv_adam_step_range(float* param, const float* grad, float* m, float* v, float* state, long long n, float beta1,
                         float beta2, float eps, float gscale, int tick, fsv_stream_t stream);
 
-/* ---- losses, D-input packing, mask pooling (csrc/losses.hip) - models/networks/loss.py:69-83,130-138;
+/* ---- losses, D-input packing, mask pooling (csrc/losses.hip) - models/networks/loss.py:17-104,130-138;
  * models/loss_collector.py:47-58,105-110,180; models/input_process.py:59 -------------------------------------------- */
 int fsv_l1_fwd(const float* a, const float* b, float bconst, const float* m, int N, int C, long long P,
                const long long* a_strides, const long long* b_strides, double* part, float* loss, fsv_stream_t stream);
@@ -512,8 +515,17 @@ int fsv_l1_bwd(const float* a, const float* b, float bconst, const float* m, int
  * array of device pointers, weights: n host floats - both travel in the kernel argument); dterms[i] = weights[i] * g[0] */
 int fsv_wsum_fwd(const float* const* terms, const float* weights, int n, float* out, fsv_stream_t stream);
 int fsv_wsum_bwd(const float* weights, int n, const float* g, float* dterms, fsv_stream_t stream);
-int fsv_hinge_fwd(const float* x, long long n, float sign, double* part, float* loss, fsv_stream_t stream);
-int fsv_hinge_bwd(const float* x, long long n, float sign, const float* gloss, float* dx, fsv_stream_t stream);
+/* the GANLoss reduction (loss.py:17-104, called with for_discriminator=True in both steps) over the n values of one prediction
+ * map, for all four objectives (mode: enum fsv_gan_mode; anything else: FSV_ERR_BAD_ARG, nothing launched).  sign = +1: the target
+ * is real (t = 1), -1: fake (t = 0).  part: double[512] scratch.  gloss: the upstream scalar g.
+ *   FSV_GAN_HINGE     loss.py:69-79   loss = -mean min(sign * x - 1, 0)                  dx_i = -g * sign * [sign * x_i < 1] / n
+ *   FSV_GAN_LS        loss.py:57-61   loss = mean (x - t)^2                  (F.mse_loss) dx_i = 2 g (x_i - t) / n
+ *   FSV_GAN_ORIGINAL  loss.py:50-53   loss = mean( max(x, 0) - x t + log1p(exp(-|x|)) )   dx_i = g (sigmoid(x_i) - t) / n
+ *                                     (F.binary_cross_entropy_with_logits; no exp of a positive argument either way)
+ *   FSV_GAN_W         loss.py:85-90   loss = -sign * mean x                               dx_i = -g * sign / n  (x is not read)
+ * The per-element term is fp32, the sums are fp64 in a fixed order (no atomics): the same bits on every run. */
+int fsv_hinge_fwd(const float* x, long long n, float sign, int mode, double* part, float* loss, fsv_stream_t stream);
+int fsv_hinge_bwd(const float* x, long long n, float sign, int mode, const float* gloss, float* dx, fsv_stream_t stream);
 int fsv_pack_d_input(const float* ref, const float* lab, const float* fake, const float* real, float* out,
                      int B, int Cr, int Cl, int Ci, long long P, const long long* ref_strides, const long long* lab_strides,
                      const long long* fake_strides, const long long* real_strides, fsv_stream_t stream);
