@@ -51,6 +51,7 @@ struct HConvP {
   int act; float scale;
   int Mz;
   int out_h, res_h;
+  int accumulate;          // add into the fp32 output the caller zeroed (no bias, residual, activation or scale: the host checked)
   long long res_bytes;     // extent of the residual tensor (0 without one)
   double* stats;
   int stats_slots, stats_ohw;
@@ -178,8 +179,8 @@ __device__ __forceinline__ void fsv_hconv_epilogue(const HConvP& p, f32x16 (&acc
         const int m = row_m(wm * (TM * 32) + i * 32 + row);
         const bool ok0 = oix[i][r] >= 0, ok1 = oix[i][r + 1] >= 0;
         float v0 = acc[i][j][r] * ws, v1 = acc[i][j][r + 1] * ws;
-        if (p.nsplit > 1) {                      // uniform
-          // split launches accumulate into a zeroed fp32 buffer (the host's workspace)
+        if (p.nsplit > 1 || p.accumulate) {      // uniform
+          // split launches accumulate into a zeroed fp32 buffer (the host's workspace), accumulating ones into the caller's
           if (ok0) atomicAdd(out_f + oix[i][r], v0);
           if (ok1) atomicAdd(out_f + oix[i][r + 1], v1);
         } else {
@@ -891,6 +892,7 @@ static int fsv_h_fill(HConvP& p, const fsv_hconv_desc& d) {
   p.Mz = d.per_sample ? d.OH * d.OW : d.N * d.OH * d.OW;
   p.nsplit = 1;
   p.out_h = d.out_h ? 1 : 0; p.res_h = d.res_h ? 1 : 0;
+  p.accumulate = d.accumulate ? 1 : 0;
   p.stats = nullptr; p.stats_slots = 1; p.stats_ohw = 1;
   return FSV_OK;
 }

@@ -136,7 +136,8 @@ int fsv_conv_wgrad(const float* in, const float* dout, float* dwt,
  * fsv_hconv_desc = one problem; n == 1: a single launch that may split K (partial sums in fp32: `ws` when the output is half) and
  * may leave normalisation statistics (stats / *produced as fsv_conv_gather_fwd_stats); n > 1: ONE grid over independent
  * problems (fsv_conv_gather_group).  res / out are half when res_h / out_h, else fp32; act FSV_ACT_DLRELU reads res as the aux
- * tensor.  FSV_ERR_UNSUPPORTED (nothing launched) for geometries outside this contract: callers keep those on the fp32 path. */
+ * tensor.  accumulate != 0: acc * wscale is ADDED into the fp32 `out` the caller zeroed (no bias, residual, activation, scale or
+ * half output: FSV_ERR_BAD_ARG).  FSV_ERR_UNSUPPORTED (nothing launched) for geometries outside this contract: callers keep those on the fp32 path. */
 typedef struct fsv_hconv_desc {
   const void* in; const void* wt; const float* bias; const void* res; void* out; const float* wscale;
   float* ws; double* stats;

@@ -696,3 +696,115 @@ def check_act_fwd(device, total, seed=120):
             berr = float(((base.double() - ref).abs() / ulp).max())
             print('%-40s kernel %.2f ulp  torch fp32 %.2f ulp' % (tag, err, berr))
             assert bool(torch.isfinite(y).all()) and err <= MARGIN * berr + 2.0, '%s: %.2f ulp against %.2f ulp' % (tag, err, berr)
+
+
+# ------------------------------------------------------------------------------------------------------ fsv_bias_act
+BIAS_ACT_TOTALS = (1, 7, 4099)                 # one value, below two float4, two passes of the grid-stride loop ending inside a pixel
+BIAS_ACT_CHANNELS = (1, 3, 64)
+
+
+def check_bias_act(device, seed=121):
+    """fsv_bias_act, in place: x = act(x + bias[i % C]) over `total` values of an NHWC tensor, every total of BIAS_ACT_TOTALS with
+    every C of BIAS_ACT_CHANNELS and every activation code of ACT_CODES (those of the convolution epilogue, and 5 = leaky 0.1).
+    The sum is ONE fp32 addition, so it equals the rounded fp64 sum bit for bit; none / relu route it, the leaky forms are one
+    more exact-product rounding (all four: bit for bit); tanh / sigmoid are compared with the fp64 function of that fp32 sum in
+    ulp of the result: at most MARGIN times the worst ulp error of torch's own fp32 tanh / sigmoid on the same sums, plus 2 ulp.
+    Guard words around x keep their bits.  Returns the number of launches.
+
+    Measured worst ulp error, kernel | torch fp32: tanh 1.28 | 0.49 on the emulator, 1.01 | 0.49 on an MI355X; sigmoid
+    0.97 | 0.94 and 1.04 | 0.94."""
+    L = lib()
+    ran = 0
+    for total in BIAS_ACT_TOTALS:
+        for C in BIAS_ACT_CHANNELS:
+            g = torch.Generator().manual_seed(seed + 100 * total + C)
+            x = torch.randn(total, generator=g) * 3.0
+            bias = torch.randn(C, generator=g)
+            edge = torch.tensor([0.0, -0.0, 50.0, -50.0])
+            k = min(total, edge.numel())
+            x[torch.arange(k) * (total // k)] = edge[:k]
+            s64 = x.double() + bias.double()[torch.arange(total) % C]
+            s = s64.float()                                            # the fp32 sum (the fp64 sum of two floats of like size is exact)
+            s64 = s.double()
+            bd = _dev(bias, device)
+            for name, code in ACT_CODES:
+                buf = _dev(torch.cat([torch.full((4,), 7.5), x, torch.full((4,), 7.5)]), device)
+                before = buf.clone()
+                y = buf[4:4 + total]
+                L.check_device(buf, bd)
+                L.call('fsv_bias_act', L.ptr(y), L.ptr(bd), total, C, code, L.stream_ptr())
+                ran += 1
+                tag = 'bias_act %s total=%d C=%d' % (name, total, C)
+                _guards_untouched(tag, buf, before, total)
+                if name == 'none':
+                    same_bits(tag, y, s)
+                elif name == 'relu':
+                    same_bits(tag, y, torch.where(s > 0, s, torch.zeros(())))
+                elif name in ('lrelu', 'lrelu01'):
+                    same_bits(tag, y, torch.where(s > 0, s, (s64 * f32(0.2 if name == 'lrelu' else 0.1)).float()))
+                else:
+                    ref = torch.tanh(s64) if name == 'tanh' else torch.sigmoid(s64)
+                    base = torch.tanh(s) if name == 'tanh' else torch.sigmoid(s)
+                    ulp = EPS32 * ref.abs().clamp_min(1e-37)
+                    err = float(((y.cpu().double() - ref).abs() / ulp).max())
+                    berr = float(((base.double() - ref).abs() / ulp).max())
+                    print('%-40s kernel %.2f ulp  torch fp32 %.2f ulp' % (tag, err, berr))
+                    assert bool(torch.isfinite(y).all()) and err <= MARGIN * berr + 2.0, '%s: %.2f ulp against %.2f ulp' % (tag, err, berr)
+    return ran
+
+
+# ------------------------------------------------------------------------------------------------------ fsv_blend_bwd
+def _ncp(t, layout, device):
+    """device copy of t [N][C][P] in `layout` -> (tensor that owns the storage, address of element (0, 0, 0), (batch, channel,
+    pixel) strides in elements)"""
+    n, c, p = t.shape
+    if layout == 'nchw':
+        d = _dev(t.contiguous(), device)
+        return d, d.data_ptr(), (c * p, p, 1)
+    if layout == 'nhwc':
+        d = _dev(t.permute(0, 2, 1).contiguous(), device)
+        return d, d.data_ptr(), (p * c, 1, c)
+    assert layout == 'slice'                   # channels 1 .. C of a wider NCHW tensor, as the generator passes image slices
+    wide = torch.full((n, c + 2, p), 1e6)
+    wide[:, 1:c + 1] = t
+    d = _dev(wide, device)
+    return d, d.data_ptr() + 4 * p, ((c + 2) * p, p, 1)
+
+
+BLEND_LAYOUTS = (('nchw', 'nhwc', 'slice'), ('nhwc', 'slice', 'nhwc'))      # of a, b and the upstream gradient g
+
+
+def check_blend_bwd(device, n=2, p=37, seed=122):
+    """fsv_blend_bwd: da, db, dm of out = a * m + b * (1 - m) (m broadcast over the channels) for an upstream gradient g, against
+    float64 autograd of that expression; C = 1 and C = 5, P = 37, a / b / g each in another memory layout (dense NCHW, dense
+    NHWC, a channel slice of a wider NCHW tensor), with all three outputs and with dm alone (da / db are nullable).  da = g * m is
+    one fp32 product: bit-equal to the rounded exact product; db and dm: `bounded` against fp32 autograd.  Returns the number of
+    launches."""
+    L = lib()
+    ll = lambda v: (ctypes.c_longlong * 3)(*v)                                  # noqa: E731
+    ran = 0
+    for c in (1, 5):
+        for la, lb, lg in BLEND_LAYOUTS:
+            g_ = torch.Generator().manual_seed(seed + c)
+            a, b, g = (torch.randn(n, c, p, generator=g_) for _ in range(3))
+            m = torch.rand(n, 1, p, generator=g_)
+            grads = {}
+            for dt in (torch.float64, torch.float32):
+                ar, br, mr = (t.to(dt).requires_grad_(True) for t in (a, b, m))
+                (ar * mr + br * (1 - mr)).backward(g.to(dt))
+                grads[dt] = (ar.grad, br.grad, mr.grad)
+            (ka, pa, sa), (kb, pb, sb), (kg, pg, sg) = _ncp(a, la, device), _ncp(b, lb, device), _ncp(g, lg, device)
+            md = _dev(m.reshape(n, p).contiguous(), device)
+            tag = 'blend_bwd C=%d a %s b %s g %s ' % (c, la, lb, lg)
+            for only_dm in (False, True):
+                da, db = (None, None) if only_dm else (torch.full((n, c, p), float('nan'), device=device) for _ in range(2))
+                dm = torch.full((n, 1, p), float('nan'), device=device)
+                L.check_device(ka, kb, kg, md, dm)
+                L.call('fsv_blend_bwd', ctypes.c_void_p(pa), ctypes.c_void_p(pb), L.ptr(md), ctypes.c_void_p(pg), L.ptr(da), L.ptr(db),
+                       L.ptr(dm), n, c, p, ll(sa), ll(sb), ll(sg), L.stream_ptr())
+                ran += 1
+                if not only_dm:
+                    same_bits(tag + 'da', da, (g.double() * m.double()).float())
+                    bounded(tag + 'db', db, grads[torch.float64][1], grads[torch.float32][1])
+                bounded(tag + ('dm alone' if only_dm else 'dm'), dm, grads[torch.float64][2], grads[torch.float32][2])
+    return ran

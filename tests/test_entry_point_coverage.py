@@ -27,7 +27,9 @@ CHECKED_BY = {
     'fsv_amp_update':                  'small_op_checks.check_amp_update',
     'fsv_avgpool3s2_bwd':              'op_checks.check_avgpool3s2',
     'fsv_avgpool3s2_fwd':              'op_checks.check_avgpool3s2',
+    'fsv_bias_act':                    'small_op_checks.check_bias_act',
     'fsv_bilinear_resize_fwd':         'op_checks.check_flownet_ops',
+    'fsv_blend_bwd':                   'small_op_checks.check_blend_bwd',
     'fsv_blend_fwd':                   'op_checks.check_warp_compose',
     'fsv_cast_half':                   'op_checks.check_spade',
     'fsv_cat_get':                     'op_checks.check_cat_and_pad',
@@ -54,6 +56,7 @@ CHECKED_BY = {
     'fsv_gather_add':                  'small_op_checks.check_gather_add',
     'fsv_hconv_gather':                'op_checks.check_spade',
     'fsv_hconv_plan':                  'host-only',
+    'fsv_hconv_prep_weight':           'h_checks.check_prep_weight_tables',
     'fsv_hconv_prep_weight_one':       'op_checks.check_spade',
     'fsv_hconv_wgrad':                 'op_checks.check_spade',
     'fsv_hinge_bwd':                   'op_checks.check_losses',
@@ -109,6 +112,7 @@ CHECKED_BY = {
     'fsv_stamp_rate_khz':              'host-only',
     'fsv_sum_terms':                   'small_op_checks.check_sum_terms',
     'fsv_unpack_d_grad':               'op_checks.check_losses',
+    'fsv_unpack_d_grad_h':             'h_checks.check_unpack_d_grad_h',
     'fsv_upload_i64':                  'small_op_checks.check_upload_i64',
     'fsv_upsample2x_bwd':              'op_checks.check_conv_up',
     'fsv_upsample2x_fwd':              'op_checks.check_conv_up',
@@ -123,13 +127,8 @@ CHECKED_BY = {
 
 # Entry points the operator-level checks do not reach yet, with where the suite does reach them.  This set may only shrink.
 NO_DIRECT_CHECK = {
-    'fsv_bias_act': "FlowNet2 teacher only (flownet2.py): reached as part of whole networks, not operator by operator",
-    'fsv_blend_bwd': "backward of ops.blend: the operator-level checks run its forward only; reached in whole training steps",
-    'fsv_hconv_prep_weight': "table-driven form behind the half-precision layout cache (hconv.py): reached in whole `--amp` steps only; "
-                             "the operator-level checks drive the one-layout form fsv_hconv_prep_weight_one",
     'fsv_pack_d_input': "no call site in the package any more (fsv_pack_d_x replaced it)",
     'fsv_pack_d_single': "no call site in the package any more (fsv_pack_d_x replaced it)",
-    'fsv_unpack_d_grad_h': "half data gradient of the first discriminator convolution: reached in whole `--amp` steps only",
 }
 
 
@@ -138,7 +137,7 @@ def test_every_entry_point_is_in_the_ledger():
     assert not set(CHECKED_BY) & set(NO_DIRECT_CHECK)
     listed = set(CHECKED_BY) | set(NO_DIRECT_CHECK)
     assert listed == declared, (sorted(declared - listed), sorted(listed - declared))
-    assert len(NO_DIRECT_CHECK) <= 6 and all(len(reason) > 20 for reason in NO_DIRECT_CHECK.values())
+    assert len(NO_DIRECT_CHECK) <= 2 and all(len(reason) > 20 for reason in NO_DIRECT_CHECK.values())
 
 
 def test_only_planning_and_measurement_entry_points_are_host_only():

@@ -53,6 +53,45 @@ def test_stats(emu_lib):
     hc.check_stats(DEV)
 
 
+@pytest.mark.parametrize('tile', hc.RAGGED_TILES)
+def test_forward_ragged(emu_lib, tile):
+    """every forced tile on shapes with a partial pixel tile, a partial channel tile, a K tail, taps outside the image, uneven
+    splits and padding workgroups, against the float64 definition, guard rows around the output"""
+    assert hc.check_forward_ragged(DEV, tile) == hc.RAGGED_CASES_PER_TILE == 14
+
+
+@pytest.mark.parametrize('tile', hc.EPILOGUE_TILES)
+@pytest.mark.parametrize('name', sorted(hc.EPILOGUE_CASES))
+def test_epilogue_options(emu_lib, name, tile):
+    hc.check_epilogue(DEV, name, tile)
+
+
+@pytest.mark.parametrize('tile', [19, 16])
+def test_group_forced_tile(emu_lib, tile):
+    assert hc.check_group_forced(DEV, tile) == 10
+
+
+def test_stats_tile_straddles_two_samples(emu_lib):
+    assert hc.check_stats_straddle(DEV, (12, 16), False) + hc.check_stats_straddle(DEV, (12, 14), True) == 2
+
+
+@pytest.mark.parametrize('gi', range(len(hc.RAGGED_WG_GEOMS)))
+def test_wgrad_ragged(emu_lib, gi):
+    assert hc.check_wgrad_ragged(DEV, gi) == len(hc.wgrad_cases(hc.RAGGED_WG_GEOMS[gi])) == (22, 22, 22, 15)[gi]
+
+
+def test_wgrad_per_sample(emu_lib):
+    assert hc.check_wgrad_per_sample(DEV) == len(hc.PER_SAMPLE_WG_CASES)
+
+
+def test_prep_weight_tables(emu_lib):
+    assert hc.check_prep_weight_tables(DEV) == 3
+
+
+def test_unpack_d_grad_h(emu_lib):
+    assert hc.check_unpack_d_grad_h(DEV) == len(hc.UNPACK_CASES)
+
+
 @pytest.mark.parametrize('nmaps,up', [(1, False), (3, True)])
 def test_spade_half_output_and_half_gradient(emu_lib, nmaps, up):
     import op_checks as oc

@@ -24,7 +24,7 @@ def test_forward_dgrad_wgrad_planned(hip_lib, gi):
     for half in (True, False):
         hc.check_forward(DEV, geom, -1, 0, half)
         hc.check_dgrad(DEV, geom, half)
-    hc.check_wgrad(DEV, geom, 0, 0)
+    assert hc.check_wgrad(DEV, geom, 0, 0) == hc.wgrad_eligible(geom)
 
 
 @pytest.mark.parametrize('tile,split', hc.FWD_TILES)
@@ -41,6 +41,45 @@ def test_wgrad_tiles(hip_lib, tile, split):
 def test_group_and_stats(hip_lib):
     hc.check_group(DEV)
     hc.check_stats(DEV)
+
+
+@pytest.mark.parametrize('tile', hc.RAGGED_TILES)
+def test_forward_ragged(hip_lib, tile):
+    """as tests/test_h_emu.py, on hardware: the LDS-direct loads, the zeros out-of-range descriptor offsets deliver, the XCD remap's
+    padding workgroups and the lane-pair half stores at ragged edges"""
+    assert hc.check_forward_ragged(DEV, tile) == hc.RAGGED_CASES_PER_TILE == 14
+
+
+@pytest.mark.parametrize('tile', hc.EPILOGUE_TILES)
+@pytest.mark.parametrize('name', sorted(hc.EPILOGUE_CASES))
+def test_epilogue_options(hip_lib, name, tile):
+    hc.check_epilogue(DEV, name, tile)
+
+
+@pytest.mark.parametrize('tile', [19, 16])
+def test_group_forced_tile(hip_lib, tile):
+    assert hc.check_group_forced(DEV, tile) == 10
+
+
+def test_stats_tile_straddles_two_samples(hip_lib):
+    assert hc.check_stats_straddle(DEV, (12, 16), False) + hc.check_stats_straddle(DEV, (12, 14), True) == 2
+
+
+@pytest.mark.parametrize('gi', range(len(hc.RAGGED_WG_GEOMS)))
+def test_wgrad_ragged(hip_lib, gi):
+    assert hc.check_wgrad_ragged(DEV, gi) == len(hc.wgrad_cases(hc.RAGGED_WG_GEOMS[gi])) == (22, 22, 22, 15)[gi]
+
+
+def test_wgrad_per_sample(hip_lib):
+    assert hc.check_wgrad_per_sample(DEV) == len(hc.PER_SAMPLE_WG_CASES)
+
+
+def test_prep_weight_tables(hip_lib):
+    assert hc.check_prep_weight_tables(DEV) == 3
+
+
+def test_unpack_d_grad_h(hip_lib):
+    assert hc.check_unpack_d_grad_h(DEV) == len(hc.UNPACK_CASES)
 
 
 @pytest.mark.parametrize('nmaps,up,c,ch,generated,hw', [(1, False, 32, 16, True, (8, 10)), (3, True, 64, 40, True, (8, 10)),

@@ -78,3 +78,11 @@ def test_two_launch_reductions(hip_lib, shape):
 @pytest.mark.parametrize("total", sc.ACT_SIZES)
 def test_act_fwd(hip_lib, total):
     sc.check_act_fwd(DEV, total)
+
+
+def test_bias_act(hip_lib):
+    assert sc.check_bias_act(DEV) == len(sc.BIAS_ACT_TOTALS) * len(sc.BIAS_ACT_CHANNELS) * len(sc.ACT_CODES) == 54
+
+
+def test_blend_bwd(hip_lib):
+    assert sc.check_blend_bwd(DEV) == 8
