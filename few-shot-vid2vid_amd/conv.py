@@ -206,7 +206,6 @@ def unprep_weight_grad(dwt, w_shape, geom, scale=None, out=None):
 # ------------------------------------------------------------------------------------------------ grouped launches
 ConvDesc, WgradDesc = lib.STRUCTS["ConvDesc"], lib.STRUCTS["WgradDesc"]
 GROUP_LIMIT = 64          # FSV_GROUP_LIMIT (csrc/conv_igemm.hip)
-_TILE_DIMS = {0: (128, 128), 1: (128, 64), 2: (128, 32), 4: (64, 64), 9: (64, 128)}
 _tls = threading.local()  # autograd runs backward on its own thread: the active group is per thread
 
 
@@ -277,7 +276,7 @@ class launch_group:
                 tile = force_tile if force_tile >= 0 else group_planned([(it[0].OH * it[0].OW * (1 if it[0].per_sample else it[0].N), it[0].Cout,
                                        (it[0].ntaps * it[0].Cin + 31) // 32, it[0].N if it[0].per_sample else 1) for it in items])
                 vec4 = all(it[0].Cin % 4 == 0 for it in items)
-                label = 'fsv_conv_igemm_group_kernel<%s,V%d>' % (profile.TILE_NAMES[tile], 4 if vec4 else 1)
+                label = 'fsv_conv_igemm_group_kernel<%s,V%d>' % (profile.tile_name(tile), 4 if vec4 else 1)
                 if _plan_log is not None:
                     _plan_log.append(('group', tile, vec4, len(items)))
         else:
@@ -650,7 +649,7 @@ def conv_dgrad(dout, w, geom, in_hw, scale=None, per_sample=False, cached=None, 
         live = [(c, sub) for c, sub in zip(geom.dgrad_classes, subs) if sub[0] > 0 and sub[1] > 0 and c['khs']]
         shapes = [((sh * sw) if per_sample else n * sh * sw, cin, (len(c['khs']) * cout + 31) // 32, n if per_sample else 1)
                   for c, (sh, sw) in live]
-        bm, bn = _TILE_DIMS[group_planned(shapes)]
+        bm, bn = profile.tile_table()[group_planned(shapes)][:2]
         wgs = sum(-(-m // bm) * -(-co // bn) * z for m, co, _, z in shapes)
         plain = plain and not (wgs <= 384 and max(k for _, _, k, _ in shapes) >= 16 and os.environ.get('FSV_DETERMINISTIC') != '1')
     elif plain:

@@ -1612,44 +1612,46 @@ static inline void fsv_pack_taps(const int* ty, const int* tx, int n, unsigned l
   }
 }
 
-// tile ids: 0 = 128x128, 1 = 128x64, 2 = 128x32, 4 = 64x64, 9 = 64x128 (BM pixels x BN output channels).  0 / 1 / 9 are
-// 8-wave workgroups (two waves per SIMD cover each other's LDS latency and barrier: +8 ... +14 % in-box over the same
-// tiles with 4 waves, profiles/r02_tile_ab.jsonl), 2 / 4 are 4-wave workgroups.
-static inline int fsv_tile_dims(int tile, int& bm, int& bn) {
-  switch (tile) {
-    case 0: bm = 128; bn = 128; return 0;
-    case 1: bm = 128; bn = 64; return 0;
-    case 2: bm = 128; bn = 32; return 0;
-    case 4: bm = 64; bn = 64; return 0;
-    case 9: bm = 64; bn = 128; return 0;
-    // experimental, force_tile only (never chosen by fsv_conv_plan): the 8-wave tiles with a prefetch distance of two chunks
-    case 10: bm = 64; bn = 128; return 0;
-    case 11: bm = 128; bn = 128; return 0;
-    case 12: bm = 128; bn = 64; return 0;
-    // 10 - 12 with the A fragments read in place (ds_read_b64 of a re-ordered quad: no select between the MFMAs; PF = 3)
-    case 13: bm = 64; bn = 128; return 0;
-    case 14: bm = 128; bn = 128; return 0;
-    case 15: bm = 128; bn = 64; return 0;
-    // the tiles that keep their global loads one chunk ahead, with in-place A fragments
-    case 16: bm = 128; bn = 128; return 0;
-    case 17: bm = 64; bn = 64; return 0;
-    case 18: bm = 128; bn = 32; return 0;
-    // 64x64 with a prefetch distance of two chunks + in-place A fragments
-    case 20: bm = 64; bn = 64; return 0;
-    // global loads straight into LDS (three buffers); the same form of the 128x128 and 128x32 tiles lost (96 / 60 KB of LDS) and was removed
-    case 21: bm = 64; bn = 128; return 0;
-    case 22: bm = 128; bn = 64; return 0;
-    case 27: bm = 64; bn = 64; return 0;
+// ---- the tile-variant table: the ONE place that knows what a force_tile id is ---------------------------------------------------
+// X(id, shape, BM, BN, WM, WN, PF, AF, MODE, DBG): BM pixels x BN output channels, WM x WN waves, then the template arguments of
+// fsv_conv_igemm_kernel (its header comment: PF = prefetch distance in chunks, AF = A fragments read in place, MODE 2 = global loads
+// straight into LDS, DBG = knock-out mask).  shape = id of the plan's tile of the same BM x BN: fsv_conv_plan picks among 0 / 1 / 2 /
+// 4 / 9 (0 / 1 / 9: 8-wave workgroups, two waves per SIMD cover each other's LDS latency and barrier, +8 ... +14 % in-box over four
+// waves, profiles/r02_tile_ab.jsonl), every other row is a kernel variant of one of them (10 - 12 PF 2, 13 - 15 PF 2 + AF, 16 - 18 AF,
+// 20 both on 64x64, 21 / 22 / 27 MODE 2: that form of 128x128 / 128x32 lost - 96 / 60 KB of LDS - and was removed).  Ids are fixed:
+// tests, tools and profiles/ name them.  Tile dimensions, variant -> shape, the cost models' "8 waves", every dispatch switch and
+// fsv_conv_tile_info (what Python reads) are derived from these rows: a variant is added or retired HERE.
+#define FSV_CONV_TILES(X)                          \
+  X(0, 0, 128, 128, 2, 4, 1, false, 0, 0)          \
+  X(1, 1, 128, 64, 4, 2, 1, false, 0, 0)           \
+  X(2, 2, 128, 32, 4, 1, 1, false, 0, 0)           \
+  X(4, 4, 64, 64, 2, 2, 1, false, 0, 0)            \
+  X(9, 9, 64, 128, 2, 4, 1, false, 0, 0)           \
+  X(10, 9, 64, 128, 2, 4, 2, false, 0, 0)          \
+  X(11, 0, 128, 128, 2, 4, 2, false, 0, 0)         \
+  X(12, 1, 128, 64, 4, 2, 2, false, 0, 0)          \
+  X(13, 9, 64, 128, 2, 4, 2, true, 0, 0)           \
+  X(14, 0, 128, 128, 2, 4, 2, true, 0, 0)          \
+  X(15, 1, 128, 64, 4, 2, 2, true, 0, 0)           \
+  X(16, 0, 128, 128, 2, 4, 1, true, 0, 0)          \
+  X(17, 4, 64, 64, 2, 2, 1, true, 0, 0)            \
+  X(18, 2, 128, 32, 4, 1, 1, true, 0, 0)           \
+  X(20, 4, 64, 64, 2, 2, 2, true, 0, 0)            \
+  X(21, 9, 64, 128, 2, 4, 2, true, 2, 0)           \
+  X(22, 1, 128, 64, 4, 2, 2, true, 2, 0)           \
+  X(27, 4, 64, 64, 2, 2, 2, true, 2, 0)
 #ifdef FSV_DIAG
-    case 30: case 31: case 32: case 33: case 34: case 35: case 36: case 37: bm = 64; bn = 128; return 0;
+// knock-out forms of the dominant kernel (tools/knockout.py; wrong results by construction, only the time is read): plain launches
+// only - the grouped, up-sampling and scalar-gather dispatchers run them as their shape, like any other variant
+#define FSV_DIAG_ROW(X, ID, DBG) X(ID, 9, 64, 128, 2, 4, 2, true, 0, DBG)
+#define FSV_CONV_TILES_DIAG(X)                                                                                   \
+  FSV_DIAG_ROW(X, 30, 1) FSV_DIAG_ROW(X, 31, 2) FSV_DIAG_ROW(X, 32, 4) FSV_DIAG_ROW(X, 33, 8) FSV_DIAG_ROW(X, 34, 16) \
+  FSV_DIAG_ROW(X, 35, 30) FSV_DIAG_ROW(X, 36, 31) FSV_DIAG_ROW(X, 37, 32)
+#else
+#define FSV_CONV_TILES_DIAG(X)
 #endif
-    default: return -1;
-  }
-}
-
-// Kernel variant a tile SHAPE of the plan (0 = 128x128, 1 = 128x64, 2 = 128x32, 4 = 64x64, 9 = 64x128) runs as.  Variants differ in
-// the prefetch distance of the global loads (PF: 1 or 2 chunks) and the A-fragment format (AF: b128 quad + per-MFMA select, or
-// re-ordered quad read in place with ds_read_b64); all are bit-equal.  Defaults = the in-box A/B of round 3
+// Kernel variant each SHAPE of the plan runs as: X(shape, id).  Variants of a shape are bit-equal except MODE 2, which pairs the k of
+// an MFMA step as (k, k + 2).  Defaults = the in-box A/B of round 3
 // (profiles/r03_notes.md, tools/tile_ab.py): 64x128 and 128x64 -> PF 2 + AF (ids 13 / 15: +6 ... +8 % over PF 2 alone, which
 // round 2 measured at +5 % over the base tile); 128x128 -> PF 1 + AF (id 16: its PF 2 forms lose occupancy - 168 registers - on
 // the multi-workgroup grids it is picked for); 64x64 -> PF 2 + AF (id 20): per shape with warm caches it equals PF 1 + AF (id 17:
@@ -1658,82 +1660,87 @@ static inline int fsv_tile_dims(int tile, int& bm, int& bn) {
 // the kernel's header comment): +3 ... +6 % per shape over id 13 (111 - 121 TFLOP/s), -0.17 ... -0.25 ms on the step (three in-box
 // triples); the LD forms of 128x64 (22) and 64x64 (27) gain per shape (+4 %, +17 % on M2048 N512 K2304) and nothing inside the step:
 // reachable, not default.  FSV_CONV_V<shape>=<id> overrides one shape (A/B runs).
+#define FSV_CONV_SHAPE_DEFAULTS(X) X(0, 16) X(1, 15) X(2, 18) X(4, 20) X(9, 21)
+// the scalar-gather kernels (Cin % 4 != 0) have no variants: X(shape, BM, BN, WM, WN), always four waves
+#define FSV_CONV_V1_SHAPES(X) X(0, 128, 128, 2, 2) X(1, 128, 64, 2, 2) X(2, 128, 32, 4, 1) X(4, 64, 64, 2, 2) X(9, 64, 128, 2, 2)
+
+struct FsvTile { int id, shape, bm, bn, wm, wn, pf, af, mode, dbg; };
+#define FSV_TILE_ROW(ID, SHAPE, BM, BN, WM, WN, PF, AF, MODE, DBG) {ID, SHAPE, BM, BN, WM, WN, PF, AF, MODE, DBG},
+static const FsvTile fsv_conv_tiles[] = {FSV_CONV_TILES(FSV_TILE_ROW) FSV_CONV_TILES_DIAG(FSV_TILE_ROW)};
+#undef FSV_TILE_ROW
+
+static inline const FsvTile* fsv_tile_row(int id) {          // nullptr: not an id
+  for (const FsvTile& t : fsv_conv_tiles)
+    if (t.id == id) return &t;
+  return nullptr;
+}
+
+extern "C" int fsv_conv_tile_info(int id, int* out) {
+  const FsvTile* t = fsv_tile_row(id);
+  if (!t || !out) return FSV_ERR_BAD_ARG;
+  out[0] = t->bm; out[1] = t->bn; out[2] = t->shape; out[3] = t->pf; out[4] = t->af; out[5] = t->mode;
+  return FSV_OK;
+}
+
+// id the plan's tile `shape` runs as: FSV_CONV_SHAPE_DEFAULTS unless FSV_CONV_V<shape> names another
 static inline int fsv_conv_variant(int shape) {
   static int map[10] = {-2, -2, -2, -2, -2, -2, -2, -2, -2, -2};
   if (shape < 0 || shape > 9) return shape;
   if (map[shape] == -2) {
-    static const int dflt[10] = {16, 15, 18, -1, 20, -1, -1, -1, -1, 21};
+    int dflt = -1;
+#define FSV_DEFAULT_OF(SHAPE, ID) if (shape == SHAPE) dflt = ID;
+    FSV_CONV_SHAPE_DEFAULTS(FSV_DEFAULT_OF)
+#undef FSV_DEFAULT_OF
     char name[16];
     snprintf(name, sizeof(name), "FSV_CONV_V%d", shape);
-    map[shape] = (int)fsv_env(name, dflt[shape]);
+    map[shape] = (int)fsv_env(name, dflt);
     if (map[shape] < 0) map[shape] = shape;
   }
   return map[shape];
 }
 
+// the folded up-sampling exists as the DEFAULT variant of each shape (FSV_CONV_V<shape> does not reach it): instantiates row
+// `DFLT` of the table with UP = true and nothing else
+template <int DFLT>
+static void fsv_launch_conv_up(const ConvP& p, dim3 g, hipStream_t stream) {
+#define FSV_UP_ROW(ID, SHAPE, BM, BN, WM, WN, PF, AF, MODE, DBG) \
+  if constexpr (ID == DFLT) FSV_LAUNCH((fsv_conv_igemm_kernel<BM, BN, WM, WN, PF, AF, DBG, MODE, true>), g, dim3(64 * WM * WN), stream, p);
+  FSV_CONV_TILES(FSV_UP_ROW)
+#undef FSV_UP_ROW
+}
+
 static int fsv_launch_conv(const ConvP& p, bool vec4, int nz, hipStream_t stream, int tile) {
-  int bm, bn;
-  if (fsv_tile_dims(tile, bm, bn)) return FSV_ERR_BAD_ARG;
-  dim3 g(fsv_cdiv(p.Mz, bm), fsv_cdiv(p.Cout, bn), nz);
+  const FsvTile* t = fsv_tile_row(tile);
+  if (!t) return FSV_ERR_BAD_ARG;
+  dim3 g(fsv_cdiv(p.Mz, t->bm), fsv_cdiv(p.Cout, t->bn), nz);
   if (p.up) {
-    // the folded up-sampling exists for the float4 gather, as the variants the plan's five tile shapes run as
-    if (!vec4) return FSV_ERR_UNSUPPORTED;
-    switch (tile) {
-      case 0: case 11: case 14: case 16: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 128, 2, 4, 1, true, 0, 0, true>), g, dim3(512), stream, p); break;
-      case 1: case 12: case 15: case 22: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 64, 4, 2, 2, true, 0, 0, true>), g, dim3(512), stream, p); break;
-      case 2: case 18: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 32, 4, 1, 1, true, 0, 0, true>), g, dim3(256), stream, p); break;
-      case 4: case 17: case 20: case 27: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 64, 2, 2, 2, true, 0, 0, true>), g, dim3(256), stream, p); break;
-      case 9: case 10: case 13: case 21: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true, 0, 2, true>), g, dim3(512), stream, p); break;
+    if (!vec4) return FSV_ERR_UNSUPPORTED;          // float4 gather only
+    switch (t->shape) {
+#define FSV_UP_CASE(SHAPE, ID) case SHAPE: fsv_launch_conv_up<ID>(p, g, stream); break;
+      FSV_CONV_SHAPE_DEFAULTS(FSV_UP_CASE)
+#undef FSV_UP_CASE
       default: return FSV_ERR_BAD_ARG;
     }
-    return fsv_check_launch();
-  }
-  if (vec4) {
+  } else if (vec4) {
     switch (tile) {
-      case 0: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 128, 2, 4>), g, dim3(512), stream, p); break;
-      case 1: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 64, 4, 2>), g, dim3(512), stream, p); break;
-      case 2: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 32, 4, 1>), g, dim3(256), stream, p); break;
-      case 4: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 64, 2, 2>), g, dim3(256), stream, p); break;
-      case 10: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2>), g, dim3(512), stream, p); break;
-      case 11: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 128, 2, 4, 2>), g, dim3(512), stream, p); break;
-      case 12: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 64, 4, 2, 2>), g, dim3(512), stream, p); break;
-      case 13: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true>), g, dim3(512), stream, p); break;
-      case 14: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 128, 2, 4, 2, true>), g, dim3(512), stream, p); break;
-      case 15: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 64, 4, 2, 2, true>), g, dim3(512), stream, p); break;
-      case 16: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 128, 2, 4, 1, true>), g, dim3(512), stream, p); break;
-      case 17: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 64, 2, 2, 1, true>), g, dim3(256), stream, p); break;
-      case 18: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 32, 4, 1, 1, true>), g, dim3(256), stream, p); break;
-      case 20: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 64, 2, 2, 2, true>), g, dim3(256), stream, p); break;
-      case 21: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true, 0, 2>), g, dim3(512), stream, p); break;
-      case 22: FSV_LAUNCH((fsv_conv_igemm_kernel<128, 64, 4, 2, 2, true, 0, 2>), g, dim3(512), stream, p); break;
-      case 27: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 64, 2, 2, 2, true, 0, 2>), g, dim3(256), stream, p); break;
-#ifdef FSV_DIAG
-      // knock-out forms of the dominant kernel (tools/knockout.py; results are wrong by construction, only the time is read)
-      case 30: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true, 1>), g, dim3(512), stream, p); break;
-      case 31: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true, 2>), g, dim3(512), stream, p); break;
-      case 32: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true, 4>), g, dim3(512), stream, p); break;
-      case 33: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true, 8>), g, dim3(512), stream, p); break;
-      case 34: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true, 16>), g, dim3(512), stream, p); break;
-      case 35: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true, 30>), g, dim3(512), stream, p); break;
-      case 36: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true, 31>), g, dim3(512), stream, p); break;
-      case 37: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4, 2, true, 32>), g, dim3(512), stream, p); break;
-#endif
-      default: FSV_LAUNCH((fsv_conv_igemm_kernel<64, 128, 2, 4>), g, dim3(512), stream, p); break;
+#define FSV_V4_CASE(ID, SHAPE, BM, BN, WM, WN, PF, AF, MODE, DBG) \
+  case ID: FSV_LAUNCH((fsv_conv_igemm_kernel<BM, BN, WM, WN, PF, AF, DBG, MODE>), g, dim3(64 * WM * WN), stream, p); break;
+      FSV_CONV_TILES(FSV_V4_CASE)
+      FSV_CONV_TILES_DIAG(FSV_V4_CASE)
+#undef FSV_V4_CASE
+      default: return FSV_ERR_BAD_ARG;
     }
   } else {
-    if (tile == 10 || tile == 13 || tile == 21) tile = 9; else if (tile == 11 || tile == 14 || tile == 16) tile = 0; else if (tile == 12 || tile == 15 || tile == 22) tile = 1;     // scalar gather: no variants
-    else if (tile == 17 || tile == 20 || tile == 27) tile = 4; else if (tile == 18) tile = 2;
-    switch (tile) {
-      case 0: FSV_LAUNCH((fsv_conv_igemm_v1_kernel<128, 128, 2, 2>), g, dim3(256), stream, p); break;
-      case 1: FSV_LAUNCH((fsv_conv_igemm_v1_kernel<128, 64, 2, 2>), g, dim3(256), stream, p); break;
-      case 2: FSV_LAUNCH((fsv_conv_igemm_v1_kernel<128, 32, 4, 1>), g, dim3(256), stream, p); break;
-      case 4: FSV_LAUNCH((fsv_conv_igemm_v1_kernel<64, 64, 2, 2>), g, dim3(256), stream, p); break;
-      default: FSV_LAUNCH((fsv_conv_igemm_v1_kernel<64, 128, 2, 2>), g, dim3(256), stream, p); break;
+    switch (t->shape) {                              // scalar gather: no variants, one kernel per shape
+#define FSV_V1_CASE(SHAPE, BM, BN, WM, WN) \
+  case SHAPE: FSV_LAUNCH((fsv_conv_igemm_v1_kernel<BM, BN, WM, WN>), g, dim3(64 * WM * WN), stream, p); break;
+      FSV_CONV_V1_SHAPES(FSV_V1_CASE)
+#undef FSV_V1_CASE
+      default: return FSV_ERR_BAD_ARG;
     }
   }
   return fsv_check_launch();
 }
-
 
 #include <stdlib.h>
 #include <string.h>
@@ -1749,7 +1756,6 @@ static inline long long fsv_tune(int which) {
 }
 
 // Tile / split-K plan shared by the launcher and (through the C ABI) by the host-side profiler labels.
-// tile ids: 0 = 128x128, 1 = 128x64, 2 = 128x32, 3 = 256x32, 4 = 64x64 (BM x BN, pixels x output channels).
 // Predicted duration (seconds) of one gather-GEMM launch with tile `tile` and `nsplit` K splits - a small cost model
 // calibrated on the in-box A/B tables (tools/tile_ab.py, profiles/r02_tile_ab.jsonl: mean error 8 %, picks within 4 % of
 // the best measured configuration on every shape):
@@ -1761,9 +1767,10 @@ static inline long long fsv_tune(int which) {
 //   * prologue + epilogue per workgroup (partly hidden when other workgroups are co-resident), a launch floor, and for
 //     split-K the zero fill, the atomics and the finishing pass.
 static inline double fsv_conv_cost(int Mz, int Cout, int nchunks, int nsamp, int tile, int nsplit) {
-  int bm, bn;
-  if (fsv_tile_dims(tile, bm, bn)) return 1e30;
-  const bool w8 = (tile == 0 || tile == 1 || tile == 9 || tile >= 10);
+  const FsvTile* row = fsv_tile_row(tile);
+  if (!row) return 1e30;
+  const int bm = row->bm, bn = row->bn;
+  const bool w8 = row->wm * row->wn >= 8;
   const double wgs = (double)fsv_cdiv(Mz, bm) * fsv_cdiv(Cout, bn) * nsamp * nsplit;
   const double L = (double)((long long)((wgs + 255.0) / 256.0));
   const double cps = (double)fsv_cdiv(nchunks, nsplit);
@@ -1783,6 +1790,19 @@ static inline double fsv_conv_cost(int Mz, int Cout, int nchunks, int nsamp, int
   return t;
 }
 
+// The plan's candidates: visit(tile, weight) for each of the five shapes that is not wider than a layer of `cout` channels needs
+// (only >= 0: that tile alone), in tie-break order - a candidate's cost counts `weight` times, so ties go to the larger tile (less
+// operand traffic per FLOP)
+template <class F>
+static inline void fsv_plan_candidates(int cout, int only, F visit) {
+  static const int tiles[5] = {0, 9, 1, 4, 2};
+  for (int ti = 0; ti < 5; ++ti) {
+    const int t = tiles[ti];
+    if (only >= 0 ? t != only : (((t == 0 || t == 9) && cout <= 64) || (t == 1 && cout <= 32) || (t == 2 && cout > 32))) continue;
+    visit(t, 1.0 + 0.01 * ti);
+  }
+}
+
 // FSV_DETERMINISTIC=1 (read at every call: tests switch it at run time): no reduction is split across workgroups, so no sum
 // depends on the arrival order of atomic adds - every gradient is a fixed-order fp32 sum.  For parity runs: exact cancellations
 // that sit ON a LeakyReLU kink otherwise take the sign the atomics' order gives them (profiles/r02_notes.md section 11: one
@@ -1800,34 +1820,25 @@ extern "C" int fsv_conv_plan(int Mz, int Cout, int nchunks, int nsamp, int force
   if (force_split <= 0 && fsv_deterministic()) force_split = 1;
   int tile = force_tile, nsplit = force_split > 0 ? force_split : 1;
   if (tile < 0 || force_split <= 0) {
-    // candidates: every tile that is not wider than the layer needs (a forced tile: only that one) x split factors that
-    // leave at least 8 chunks (256 K-elements) per split; ties go to the larger tile (less operand traffic per FLOP)
-    static const int tiles[5] = {0, 9, 1, 4, 2};
+    // every candidate tile (a forced tile: only that one, and only if it is one of the five shapes) x split factors that leave at
+    // least 8 chunks (256 K-elements) per split
     static const int splits[6] = {1, 2, 3, 4, 6, 8};
     double best = 1e30;
     int bt = -1, bs = 1;
-    for (int ti = 0; ti < 5; ++ti) {
-      const int t = tiles[ti];
-      if (force_tile >= 0 && t != force_tile) continue;
-      if (force_tile < 0) {
-        if ((t == 0 || t == 9) && Cout <= 64) continue;
-        if (t == 1 && Cout <= 32) continue;
-        if (t == 2 && Cout > 32) continue;
-      }
+    fsv_plan_candidates(Cout, force_tile, [&](int t, double weight) {
       for (int si = 0; si < 6; ++si) {
         const int sp = splits[si];
         if (force_split > 0 && sp != 1) break;
         const int use = force_split > 0 ? force_split : sp;
         if (use > 1 && nchunks / use < 8) break;
-        const double c = fsv_conv_cost(Mz, Cout, nchunks, nsamp, t, use) * (1.0 + 0.01 * ti);
+        const double c = fsv_conv_cost(Mz, Cout, nchunks, nsamp, t, use) * weight;
         if (c < best) { best = c; bt = t; bs = use; }
       }
-    }
+    });
     if (bt < 0) { bt = force_tile >= 0 ? force_tile : (Cout <= 32 ? 2 : 4); bs = force_split > 0 ? force_split : 1; }
     tile = bt; nsplit = bs;
   }
-  int bm, bn;
-  if (fsv_tile_dims(tile, bm, bn)) return -1;
+  if (!fsv_tile_row(tile)) return -1;
   if (nsplit > nchunks) nsplit = nchunks;
   if (nsplit < 1) nsplit = 1;
   *tile_out = tile; *nsplit_out = nsplit;
@@ -1861,6 +1872,18 @@ static inline void fsv_fill_convp(ConvP& p, const float* in, const float* wt, co
 
 static inline bool vec4_ok(int cin) { return (cin & 3) == 0; }
 
+// what every gather-GEMM launch needs of its arguments, single or grouped
+static inline int fsv_conv_check_args(const float* in, const float* wt, const float* out, int N, int H, int W, int Cin, int Cout,
+                                      int ntaps, const int* ty, const int* tx, int ldw) {
+  if (!in || !wt || !out || ntaps < 1 || ntaps > 16 || N < 1 || Cin < 1 || Cout < 1) return FSV_ERR_BAD_ARG;
+  for (int t = 0; t < ntaps; ++t)
+    if (ty[t] < -8 || ty[t] > 7 || tx[t] < -8 || tx[t] > 7) return FSV_ERR_UNSUPPORTED;          // taps are packed into 4 bits each
+  if ((ldw & 3) != 0 || ldw < Cout) return FSV_ERR_BAD_ARG;
+  // the V4 kernels index one tensor / one weight matrix with 32-bit element offsets
+  if ((long long)N * H * W * Cin * 4 > FSV_BUF_MAX_BYTES || (long long)(ntaps * Cin + 32) * ldw * 4 > FSV_BUF_MAX_BYTES) return FSV_ERR_UNSUPPORTED;
+  return FSV_OK;
+}
+
 // Generic gather-GEMM (see header comment and include/fsv2v.h: fsv_conv_gather_fwd).  stats / stats_groups / stats_slots:
 // optional statistics partials for the normalisation that follows (ConvP::stats); *produced tells whether this launch wrote
 // them (not when the plan splits K or the layer takes the scalar-gather kernel: the caller then runs its reduction pass).
@@ -1872,14 +1895,9 @@ static int fsv_conv_gather_impl(const float* in, const float* wt, const float* b
                         int act, float scale, int force_tile, int force_split, int accumulate, const float* wscale,
                         double* stats, int stats_groups, int stats_slots, int stats_prezeroed, int* produced,
                         float* split_ws, long long split_cap, int in_up, hipStream_t stream) {
-  if (!in || !wt || !out || ntaps < 1 || ntaps > 16 || N < 1 || Cin < 1 || Cout < 1) return FSV_ERR_BAD_ARG;
-  for (int t = 0; t < ntaps; ++t)
-    if (ty[t] < -8 || ty[t] > 7 || tx[t] < -8 || tx[t] > 7) return FSV_ERR_UNSUPPORTED;
-  if ((ldw & 3) != 0 || ldw < Cout) return FSV_ERR_BAD_ARG;
+  if (const int bad = fsv_conv_check_args(in, wt, out, N, H, W, Cin, Cout, ntaps, ty, tx, ldw)) return bad;
   // in_up: the input is stored at H / 2 x W / 2 and read through the nearest x2 index (ConvP::up); float4 gather, MFMA tiles only
   if (in_up && ((H & 1) || (W & 1) || (Cin % 4 != 0) || per_sample || accumulate || Cout <= 4)) return FSV_ERR_UNSUPPORTED;
-  // the V4 kernels index one tensor / one weight matrix with 32-bit element offsets
-  if ((long long)N * H * W * Cin * 4 > FSV_BUF_MAX_BYTES || (long long)(ntaps * Cin + 32) * ldw * 4 > FSV_BUF_MAX_BYTES) return FSV_ERR_UNSUPPORTED;
   ConvP p;
   fsv_fill_convp(p, in, wt, bias, res, out, wscale, N, H, W, Cin, OH, OW, Cout, ntaps, ty, tx, sy, sx, outH, outW, osy, osx, ooy,
                  oox, ldw, w_bstride, b_bstride, per_sample, act, scale);
@@ -2021,6 +2039,23 @@ int fsv_bias_act(float* x, const float* bias, long long total, int C, int act, h
   return fsv_check_launch();
 }
 
+}  // extern "C"
+
+static inline void fsv_fill_wgradp(WgradP& p, const float* in, const float* dout, float* dwt, int N, int H, int W, int Cin, int OH,
+                                   int OW, int Cout, int ntaps, const int* ty, const int* tx, int sy, int sx, int ldw,
+                                   long long w_bstride, int per_sample, int in_up) {
+  p.in = in; p.dout = dout; p.dwt = dwt;
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.Cout = Cout;
+  p.K = ntaps * Cin; p.ldw = ldw; p.sy = sy; p.sx = sx; p.ntaps = ntaps;
+  fsv_pack_taps(ty, tx, ntaps, p.taps_lo, p.taps_hi, 8);
+  p.w_bstride = w_bstride; p.per_sample = per_sample ? 1 : 0;
+  p.Mz = per_sample ? OH * OW : N * OH * OW;
+  p.pchunks = fsv_cdiv(p.Mz, FSV_BK);
+  p.up = in_up ? 1 : 0;
+}
+
+extern "C" {
+
 int fsv_conv_wgrad(const float* in, const float* dout, float* dwt,
                    int N, int H, int W, int Cin, int OH, int OW, int Cout,
                    int ntaps, const int* ty, const int* tx, int sy, int sx,
@@ -2034,14 +2069,7 @@ int fsv_conv_wgrad(const float* in, const float* dout, float* dwt,
     if (ty[t] < -8 || ty[t] > 7 || tx[t] < -8 || tx[t] > 7) return FSV_ERR_UNSUPPORTED;
   if ((long long)N * H * W * Cin * 4 > FSV_BUF_MAX_BYTES || (long long)N * OH * OW * Cout * 4 > FSV_BUF_MAX_BYTES) return FSV_ERR_UNSUPPORTED;      // 32-bit byte offsets
   WgradP p;
-  p.in = in; p.dout = dout; p.dwt = dwt;
-  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.Cout = Cout;
-  p.K = ntaps * Cin; p.ldw = ldw; p.sy = sy; p.sx = sx; p.ntaps = ntaps;
-  fsv_pack_taps(ty, tx, ntaps, p.taps_lo, p.taps_hi, 8);
-  p.w_bstride = w_bstride; p.per_sample = per_sample ? 1 : 0;
-  p.Mz = per_sample ? OH * OW : N * OH * OW;
-  p.pchunks = fsv_cdiv(p.Mz, FSV_BK);
-  p.up = in_up ? 1 : 0;
+  fsv_fill_wgradp(p, in, dout, dwt, N, H, W, Cin, OH, OW, Cout, ntaps, ty, tx, sy, sx, ldw, w_bstride, per_sample, in_up);
   const int nsamp = per_sample ? N : 1;
   if (Cout <= 4 && vec4_ok(Cin) && !per_sample && force_tile == 0 && force_split <= 0 && ntaps * (Cin >> 2) <= 256 &&
       fsv_conv_thin(p.Mz, p.K)) {
@@ -2131,9 +2159,10 @@ int fsv_prep_weight(const float* w, float* wt, const float* scale_ptr, int mode,
 
 // ---- grouped launches (include/fsv2v.h: fsv_conv_gather_group / fsv_conv_wgrad_group) ------------------------------------
 static inline double fsv_group_cost(const ConvP* ps, const int* nsamp, int n, int tile) {
-  int bm, bn;
-  if (fsv_tile_dims(tile, bm, bn)) return 1e30;
-  const bool w8 = (tile == 0 || tile == 1 || tile == 9);
+  const FsvTile* row = fsv_tile_row(tile);
+  if (!row) return 1e30;
+  const int bm = row->bm, bn = row->bn;
+  const bool w8 = row->wm * row->wn >= 8;
   const double cyc = (double)bm * bn / 4.0;
   const double ovh = 5000.0 + bm * bn / 8.0;
   double load = 0.0, crit = 0.0;
@@ -2146,6 +2175,20 @@ static inline double fsv_group_cost(const ConvP* ps, const int* nsamp, int n, in
   }
   load /= 256.0;
   return (load > crit ? load : crit) / 1.95e9 + 4e-6;
+}
+
+// one tile shape for a whole group: the cheapest candidate for its widest problem (only Mz, Cout, nchunks of `ps` are read)
+static inline int fsv_group_tile(const ConvP* ps, const int* nsamp, int n) {
+  int max_cout = 0;
+  for (int i = 0; i < n; ++i)
+    if (ps[i].Cout > max_cout) max_cout = ps[i].Cout;
+  double best = 1e30;
+  int tile = 4;
+  fsv_plan_candidates(max_cout, -1, [&](int t, double weight) {
+    const double c = fsv_group_cost(ps, nsamp, n, t) * weight;
+    if (c < best) { best = c; tile = t; }
+  });
+  return tile;
 }
 
 static inline void fsv_group_order(const long long* weight, int n, int* order) {
@@ -2168,15 +2211,9 @@ int fsv_conv_gather_group(const fsv_conv_desc* d, int n, int force_tile, hipStre
   int nsamp[FSV_GROUP_LIMIT];
   long long weight[FSV_GROUP_LIMIT];
   bool vec4 = true;
-  int max_cout = 0;
   for (int i = 0; i < n; ++i) {
     const fsv_conv_desc& q = d[i];
-    if (!q.in || !q.wt || !q.out || q.ntaps < 1 || q.ntaps > 16 || q.N < 1 || q.Cin < 1 || q.Cout < 1) return FSV_ERR_BAD_ARG;
-    for (int t = 0; t < q.ntaps; ++t)
-      if (q.ty[t] < -8 || q.ty[t] > 7 || q.tx[t] < -8 || q.tx[t] > 7) return FSV_ERR_UNSUPPORTED;
-    if ((q.ldw & 3) != 0 || q.ldw < q.Cout) return FSV_ERR_BAD_ARG;
-    if ((long long)q.N * q.H * q.W * q.Cin * 4 > FSV_BUF_MAX_BYTES || (long long)(q.ntaps * q.Cin + 32) * q.ldw * 4 > FSV_BUF_MAX_BYTES)
-      return FSV_ERR_UNSUPPORTED;
+    if (const int bad = fsv_conv_check_args(q.in, q.wt, q.out, q.N, q.H, q.W, q.Cin, q.Cout, q.ntaps, q.ty, q.tx, q.ldw)) return bad;
     if (q.accumulate && (q.bias || q.res || q.act != FSV_ACT_NONE || q.scale != 1.f)) return FSV_ERR_BAD_ARG;
     if (q.act == FSV_ACT_DLRELU && !q.res) return FSV_ERR_BAD_ARG;
     fsv_fill_convp(ps[i], q.in, q.wt, q.bias, q.res, q.out, q.wscale, q.N, q.H, q.W, q.Cin, q.OH, q.OW, q.Cout, q.ntaps, q.ty,
@@ -2184,26 +2221,12 @@ int fsv_conv_gather_group(const fsv_conv_desc* d, int n, int force_tile, hipStre
                    q.act, q.scale);
     nsamp[i] = q.per_sample ? q.N : 1;
     vec4 = vec4 && vec4_ok(q.Cin);
-    if (q.Cout > max_cout) max_cout = q.Cout;
   }
-  // one tile shape for the whole group
-  int tile = force_tile;
-  if (tile < 0) {
-    static const int tiles[5] = {0, 9, 1, 4, 2};
-    double best = 1e30;
-    for (int ti = 0; ti < 5; ++ti) {
-      const int t = tiles[ti];
-      if ((t == 0 || t == 9) && max_cout <= 64) continue;
-      if (t == 1 && max_cout <= 32) continue;
-      if (t == 2 && max_cout > 32) continue;
-      const double c = fsv_group_cost(ps, nsamp, n, t) * (1.0 + 0.01 * ti);
-      if (c < best) { best = c; tile = t; }
-    }
-    if (tile < 0) tile = 4;
-  }
-  if (tile >= 10) tile = (tile == 10 || tile == 13 || tile == 21) ? 9 : (tile == 11 || tile == 14 || tile == 16) ? 0 : (tile == 17 || tile == 20 || tile == 27) ? 4 : (tile == 18) ? 2 : 1;
-  int bm, bn;
-  if (fsv_tile_dims(tile, bm, bn)) return FSV_ERR_BAD_ARG;
+  // one tile shape for the whole group.  A forced id counts for its SHAPE only: like a planned shape it then runs as that shape's
+  // current variant (fsv_conv_variant), so forcing 13 here launches what forcing 9 launches
+  const FsvTile* row = fsv_tile_row(force_tile < 0 ? fsv_group_tile(ps, nsamp, n) : force_tile);
+  if (!row) return FSV_ERR_BAD_ARG;
+  const int tile = row->shape, bm = row->bm, bn = row->bn;
   // K splits: only problems that accumulate into a zeroed output, and only when the whole group would leave CUs idle
   long long wgs1 = 0;
   for (int i = 0; i < n; ++i) wgs1 += (long long)fsv_cdiv(ps[i].Mz, bm) * fsv_cdiv(ps[i].Cout, bn) * nsamp[i];
@@ -2241,33 +2264,19 @@ int fsv_conv_gather_group(const fsv_conv_desc* d, int n, int force_tile, hipStre
     const dim3 grid(tiles);
     if (vec4) {
       switch (variant) {
-        case 0: FSV_LAUNCH((fsv_conv_igemm_group_kernel<128, 128, 2, 4>), grid, dim3(512), stream, g); break;
-        case 1: FSV_LAUNCH((fsv_conv_igemm_group_kernel<128, 64, 4, 2>), grid, dim3(512), stream, g); break;
-        case 2: FSV_LAUNCH((fsv_conv_igemm_group_kernel<128, 32, 4, 1>), grid, dim3(256), stream, g); break;
-        case 4: FSV_LAUNCH((fsv_conv_igemm_group_kernel<64, 64, 2, 2>), grid, dim3(256), stream, g); break;
-        case 9: FSV_LAUNCH((fsv_conv_igemm_group_kernel<64, 128, 2, 4>), grid, dim3(512), stream, g); break;
-        case 10: FSV_LAUNCH((fsv_conv_igemm_group_kernel<64, 128, 2, 4, 2>), grid, dim3(512), stream, g); break;
-        case 11: FSV_LAUNCH((fsv_conv_igemm_group_kernel<128, 128, 2, 4, 2>), grid, dim3(512), stream, g); break;
-        case 12: FSV_LAUNCH((fsv_conv_igemm_group_kernel<128, 64, 4, 2, 2>), grid, dim3(512), stream, g); break;
-        case 13: FSV_LAUNCH((fsv_conv_igemm_group_kernel<64, 128, 2, 4, 2, true>), grid, dim3(512), stream, g); break;
-        case 14: FSV_LAUNCH((fsv_conv_igemm_group_kernel<128, 128, 2, 4, 2, true>), grid, dim3(512), stream, g); break;
-        case 15: FSV_LAUNCH((fsv_conv_igemm_group_kernel<128, 64, 4, 2, 2, true>), grid, dim3(512), stream, g); break;
-        case 16: FSV_LAUNCH((fsv_conv_igemm_group_kernel<128, 128, 2, 4, 1, true>), grid, dim3(512), stream, g); break;
-        case 17: FSV_LAUNCH((fsv_conv_igemm_group_kernel<64, 64, 2, 2, 1, true>), grid, dim3(256), stream, g); break;
-        case 18: FSV_LAUNCH((fsv_conv_igemm_group_kernel<128, 32, 4, 1, 1, true>), grid, dim3(256), stream, g); break;
-        case 20: FSV_LAUNCH((fsv_conv_igemm_group_kernel<64, 64, 2, 2, 2, true>), grid, dim3(256), stream, g); break;
-        case 21: FSV_LAUNCH((fsv_conv_igemm_group_kernel<64, 128, 2, 4, 2, true, 2>), grid, dim3(512), stream, g); break;
-        case 22: FSV_LAUNCH((fsv_conv_igemm_group_kernel<128, 64, 4, 2, 2, true, 2>), grid, dim3(512), stream, g); break;
-        case 27: FSV_LAUNCH((fsv_conv_igemm_group_kernel<64, 64, 2, 2, 2, true, 2>), grid, dim3(256), stream, g); break;
+#define FSV_GROUP_CASE(ID, SHAPE, BM, BN, WM, WN, PF, AF, MODE, DBG) \
+  case ID: FSV_LAUNCH((fsv_conv_igemm_group_kernel<BM, BN, WM, WN, PF, AF, MODE>), grid, dim3(64 * WM * WN), stream, g); break;
+        FSV_CONV_TILES(FSV_GROUP_CASE)
+#undef FSV_GROUP_CASE
         default: return FSV_ERR_BAD_ARG;
       }
     } else {
       switch (tile) {
-        case 0: FSV_LAUNCH((fsv_conv_igemm_v1_group_kernel<128, 128, 2, 2>), grid, dim3(256), stream, g); break;
-        case 1: FSV_LAUNCH((fsv_conv_igemm_v1_group_kernel<128, 64, 2, 2>), grid, dim3(256), stream, g); break;
-        case 2: FSV_LAUNCH((fsv_conv_igemm_v1_group_kernel<128, 32, 4, 1>), grid, dim3(256), stream, g); break;
-        case 4: FSV_LAUNCH((fsv_conv_igemm_v1_group_kernel<64, 64, 2, 2>), grid, dim3(256), stream, g); break;
-        default: FSV_LAUNCH((fsv_conv_igemm_v1_group_kernel<64, 128, 2, 2>), grid, dim3(256), stream, g); break;
+#define FSV_V1_GROUP_CASE(SHAPE, BM, BN, WM, WN) \
+  case SHAPE: FSV_LAUNCH((fsv_conv_igemm_v1_group_kernel<BM, BN, WM, WN>), grid, dim3(64 * WM * WN), stream, g); break;
+        FSV_CONV_V1_SHAPES(FSV_V1_GROUP_CASE)
+#undef FSV_V1_GROUP_CASE
+        default: return FSV_ERR_BAD_ARG;
       }
     }
   }
@@ -2278,20 +2287,8 @@ int fsv_conv_gather_group(const fsv_conv_desc* d, int n, int force_tile, hipStre
 int fsv_conv_group_plan(const int* Mz, const int* Cout, const int* nchunks, const int* nsamp, int n, int* tile_out) {
   if (!Mz || !Cout || !nchunks || !nsamp || !tile_out || n < 1 || n > FSV_GROUP_LIMIT) return FSV_ERR_BAD_ARG;
   ConvP ps[FSV_GROUP_LIMIT];
-  int max_cout = 0;
-  for (int i = 0; i < n; ++i) { ps[i].Mz = Mz[i]; ps[i].Cout = Cout[i]; ps[i].nchunks = nchunks[i]; if (Cout[i] > max_cout) max_cout = Cout[i]; }
-  static const int tiles[5] = {0, 9, 1, 4, 2};
-  double best = 1e30;
-  int tile = 4;
-  for (int ti = 0; ti < 5; ++ti) {
-    const int t = tiles[ti];
-    if ((t == 0 || t == 9) && max_cout <= 64) continue;
-    if (t == 1 && max_cout <= 32) continue;
-    if (t == 2 && max_cout > 32) continue;
-    const double c = fsv_group_cost(ps, nsamp, n, t) * (1.0 + 0.01 * ti);
-    if (c < best) { best = c; tile = t; }
-  }
-  *tile_out = tile;
+  for (int i = 0; i < n; ++i) { ps[i].Mz = Mz[i]; ps[i].Cout = Cout[i]; ps[i].nchunks = nchunks[i]; }
+  *tile_out = fsv_group_tile(ps, nsamp, n);
   return FSV_OK;
 }
 
@@ -2315,13 +2312,8 @@ int fsv_conv_wgrad_group(const fsv_wgrad_desc* d, int n, hipStream_t stream) {
       return FSV_ERR_UNSUPPORTED;
     if (!vec4_ok(q.Cin) || !(FSV_BK / q.OW + 1 <= q.OH)) return FSV_ERR_UNSUPPORTED;
     WgradP& p = ps[i];
-    p.in = q.in; p.dout = q.dout; p.dwt = q.dwt;
-    p.N = q.N; p.H = q.H; p.W = q.W; p.Cin = q.Cin; p.OH = q.OH; p.OW = q.OW; p.Cout = q.Cout;
-    p.K = q.ntaps * q.Cin; p.ldw = q.ldw; p.sy = q.sy; p.sx = q.sx; p.ntaps = q.ntaps;
-    fsv_pack_taps(q.ty, q.tx, q.ntaps, p.taps_lo, p.taps_hi, 8);
-    p.w_bstride = q.w_bstride; p.per_sample = q.per_sample ? 1 : 0;
-    p.Mz = q.per_sample ? q.OH * q.OW : q.N * q.OH * q.OW;
-    p.pchunks = fsv_cdiv(p.Mz, FSV_BK); p.up = 0;
+    fsv_fill_wgradp(p, q.in, q.dout, q.dwt, q.N, q.H, q.W, q.Cin, q.OH, q.OW, q.Cout, q.ntaps, q.ty, q.tx, q.sy, q.sx, q.ldw,
+                    q.w_bstride, q.per_sample, 0);
     nsamp[i] = q.per_sample ? q.N : 1;
     cout4 = cout4 && (q.Cout & 3) == 0;
     blocks += (long long)fsv_cdiv(p.K, 64) * fsv_cdiv(q.Cout, 64) * nsamp[i];

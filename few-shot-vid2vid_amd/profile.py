@@ -26,8 +26,23 @@ _records = []          # (label, flops, ev0, ev1)
 FP32_MFMA_PEAK = 157.3e12
 F16_MFMA_PEAK = 2.5e15        # dense f16 / bf16 matrix peak (MI355X_MICROARCH.md; the 2:1-sparse figure is not used)
 
-TILE_NAMES = {0: '128x128', 1: '128x64', 2: '128x32', 4: '64x64', 9: '64x128', 10: '64x128pf2', 11: '128x128pf2', 12: '128x64pf2',
-              13: '64x128pf2af', 14: '128x128pf2af', 15: '128x64pf2af', 16: '128x128af', 17: '64x64af', 18: '128x32af', 20: '64x64pf2af', 21: '64x128lds', 22: '128x64lds', 27: '64x64lds'}
+_tiles = None
+
+
+def tile_table():
+    """id -> (bm, bn, shape, pf, af, mode): the tile-variant table of the fp32 gather-GEMM (csrc/conv_igemm.hip FSV_CONV_TILES), read
+    from the library once"""
+    global _tiles
+    if _tiles is None:
+        out = (ctypes.c_int * 6)()
+        _tiles = {i: tuple(out) for i in range(64) if lib.call_status("fsv_conv_tile_info", i, out) == 0}
+    return _tiles
+
+
+def tile_name(tile):
+    """'64x128pf2af': tools/trace_by_grid.py, tools/launch_report.py and the CSVs under profiles/ match on these strings"""
+    bm, bn, _, pf, af, mode = tile_table()[tile]
+    return '%dx%d' % (bm, bn) + ('lds' if mode == 2 else ('pf2' if pf == 2 else '') + ('af' if af else ''))
 
 
 _events = True        # False: labels are produced (scopes are entered) but no HIP events are recorded - a stamped graph capture
@@ -146,7 +161,7 @@ def conv_label(mz, cout, nchunks, nsamp, vec4, force_tile=-1, force_split=0, thi
         return base
     tile, nsplit = ctypes.c_int(0), ctypes.c_int(1)
     lib.call("fsv_conv_plan", mz, cout, nchunks, nsamp, force_tile, force_split, ctypes.byref(tile), ctypes.byref(nsplit))
-    base = 'fsv_conv_igemm_kernel<%s,V%d>' % (TILE_NAMES[tile.value], 4 if vec4 else 1)
+    base = 'fsv_conv_igemm_kernel<%s,V%d>' % (tile_name(tile.value), 4 if vec4 else 1)
     if _detail:
         base += ' M%d N%d K%d z%d split%d' % (mz, cout, nchunks * 32, nsamp, nsplit.value)
     return base

@@ -49,9 +49,8 @@ enum fsv_gan_mode { FSV_GAN_HINGE = 0 /* loss.py:69-79 */, FSV_GAN_LS = 1 /* :57
  * taps outside the input read as zero.  wt: K-major [Kpad][ldw] from fsv_prep_weight; per_sample != 0 selects one
  * weight matrix (stride w_bstride) and bias (stride b_bstride) per sample n.  accumulate != 0: `out` was zeroed by
  * the caller, results are added (used for the four parity classes of a stride-2 data gradient).
- * force_tile / force_split: -1 / 0 = automatic (tile ids, pixels x channels: 0 128x128, 1 128x64, 2 128x32, 4 64x64, 9 64x128;
- * 10 / 11 / 12 = 64x128 / 128x128 / 128x64 with the global loads two chunks ahead: what the plan's 9 / 0 / 1 run as unless
- * FSV_CONV_PF2=0).
+ * force_tile / force_split: -1 / 0 = automatic; a tile id is a row of the tile-variant table (csrc/conv_igemm.hip FSV_CONV_TILES,
+ * readable through fsv_conv_tile_info): FSV_ERR_BAD_ARG for any other id.
  * One activation tensor / weight matrix may hold at most 2 GiB (32-bit byte offsets): FSV_ERR_UNSUPPORTED beyond.  wscale: optional device scalar multiplying the accumulator before
  * the bias (the spectral-norm 1/sigma when wt holds un-normalised weights). */
 /* split_ws / split_ws_floats (nullable; ordered split-K): when the call's plan splits K, split k stores its partial output into
@@ -119,8 +118,8 @@ int fsv_conv_gather_fwd_stats(const float* in, const float* wt, const float* bia
 int fsv_bias_act(float* x, const float* bias, long long total, int C, int act, fsv_stream_t stream);
 /* dwt[t*Cin+ci][co] = sum_{n,oy,ox} in[n, oy*sy+ty[t], ox*sx+tx[t], ci] * dout[n, oy, ox, co]  (weight gradient)
  * prezeroed: dwt already holds zeros (a slice of the optimiser's per-pass arena), skip the split-K zero-fill;
- * force_tile: 0 = automatic (1 / 2 / 3 = 64x64 / 128x64 / 64x128 rows x columns, 5 / 6 = 64x64 / 64x128 as one- / two-wave
- * workgroups, 7 / 8 = the same two tiles with double-buffered LDS; for A/B runs) */
+ * force_tile: 0 = the launcher's plan, 1 / 2 / 3 / 4 = 64x64 / 128x64 / 64x128 / 128x128 rows x columns (float4-gather layers wide
+ * enough for the tile, else ignored; for A/B runs) */
 int fsv_conv_wgrad(const float* in, const float* dout, float* dwt,
                    int N, int H, int W, int Cin, int OH, int OW, int Cout,
                    int ntaps, const int* ty, const int* tx, int sy, int sx,
@@ -239,6 +238,10 @@ int fsv_upload_i64(long long* dst, const long long* host_src, int n, fsv_stream_
 /* tile / split-K plan the launcher will use (exported so host-side profilers label launches consistently) */
 int fsv_conv_plan(int Mz, int Cout, int nchunks, int nsamp, int force_tile, int force_split, int* tile_out,
                   int* nsplit_out);
+/* row `id` of the gather-GEMM's tile-variant table (csrc/conv_igemm.hip FSV_CONV_TILES): out = {BM pixels, BN channels, id of the
+ * plan's tile of that shape, prefetch distance, in-place A fragments, mode (2 = loads straight into LDS)}; FSV_ERR_BAD_ARG when
+ * no such row exists - for labels and tests, like fsv_conv_plan */
+int fsv_conv_tile_info(int id, int* out /* bm, bn, shape, pf, af, mode */);
 /* 1 when a Cout <= 4 layer of Mz pixels and K = taps * Cin takes the vector-ALU kernels (fsv_conv_thin_*), else 0 - NOT a status;
  * for profiler labels, like fsv_conv_plan */
 int fsv_conv_thin_rule(int Mz, int K);

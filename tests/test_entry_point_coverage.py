@@ -13,7 +13,7 @@ import re
 from test_abi import declared_symbols
 
 HOST_ONLY = "host-only"          # measurement-only and planning entry points: nothing to compare with a reference
-_HOST_ONLY_NAMES = re.compile(r"^fsv_stamp|_plan$|_rule$|_supported$|_workspace_doubles$|_scratch_floats$")
+_HOST_ONLY_NAMES = re.compile(r"^fsv_stamp|_plan$|_rule$|_info$|_supported$|_workspace_doubles$|_scratch_floats$")
 
 CHECKED_BY = {
     'fsv_act_bwd':                     'op_checks.check_conv',
@@ -46,6 +46,7 @@ CHECKED_BY = {
     'fsv_conv_group_plan':             'host-only',
     'fsv_conv_plan':                   'host-only',
     'fsv_conv_thin_rule':              'host-only',
+    'fsv_conv_tile_info':              'host-only',
     'fsv_conv_wgrad':                  'op_checks.check_conv',
     'fsv_conv_wgrad_group':            'op_checks.check_conv_groups',
     'fsv_conv_wgrad_np':               'np_checks.check_wgrad',

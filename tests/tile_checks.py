@@ -36,6 +36,13 @@ REORDERED_FWD_TILES = (21, 22, 27)
 WGRAD_TILES = (0, 1, 2, 3, 4)
 
 
+def tile_table():
+    """id -> (bm, bn, shape, pf, af, mode) of every tile id the library knows (fsv_conv_tile_info)"""
+    from importlib import import_module
+    oc.pkg()
+    return import_module('few-shot-vid2vid_amd.profile').tile_table()
+
+
 def _fwd_case(device, geom, tile, split, seed):
     ops, conv = oc.pkg()
     n, cin, h, w, cout, k, s, p = geom
@@ -55,7 +62,7 @@ def _fwd_case(device, geom, tile, split, seed):
 def check_forward_tiles(device, tiles=FWD_TILES, geoms=GEOMS):
     for gi, geom in enumerate(geoms):
         for tile in tiles:
-            bn = {0: 128, 1: 64, 2: 32, 4: 64, 9: 128, 10: 128, 11: 128, 12: 64, 13: 128, 14: 128, 15: 64, 16: 128, 17: 64, 18: 32, 20: 64, 21: 128, 22: 64, 27: 64}[tile]
+            bn = tile_table()[tile][1]
             if geom[4] < bn // 2 and bn > 32:
                 continue                       # a tile twice as wide as the layer: not a configuration the plan can produce
             for split in (1, 3):
@@ -113,7 +120,81 @@ def check_wgrad_tiles(device, tiles=WGRAD_TILES, geoms=GEOMS):
                 oc.assert_close('wgrad tile %d split %d %s' % (tile, split, geom), dw, wt.grad, 2e-5)
 
 
+def _status(fn):
+    """fsv_status a library call inside fn() fails with (0: it does not fail)"""
+    import re
+    from importlib import import_module
+    oc.pkg()
+    try:
+        fn()
+    except import_module('few-shot-vid2vid_amd.lib').FsvError as e:
+        return int(re.search(r'fsv_status (-?\d+)', str(e)).group(1))
+    return 0
+
+
+def _walk_paths(device):
+    """the four dispatchers of the fp32 gather-GEMM as name -> (run(tile) -> outputs, F.conv2d references), on the smallest shapes
+    that still have a partial tile on both axes (a K tail chunk too where Cin allows); inputs and references are made once"""
+    ops, conv = oc.pkg()
+    g = torch.Generator().manual_seed(500)
+
+    def problem(n, cin, h, w, cout, k):
+        x = torch.randn(n, cin, h, w, generator=g)
+        wt = torch.randn(cout, cin, k, k, generator=g) * (1.0 / (cin * k * k) ** 0.5)
+        ge = conv.Geom(k, k, 1, k // 2)
+        wf, _, ldw = conv.prep_weight(wt.to(device), 0, ge)
+        return x, wt, conv.to_nhwc(x.to(device)), wf, ldw, cout, ge
+
+    def single(prob, up=False):
+        x, wt, xd, wf, ldw, cout, ge = prob
+        ref = F.conv2d(F.interpolate(x, scale_factor=2) if up else x, wt, padding=ge.pad)
+        return (lambda tile: [conv.conv_forward(xd, wf, ldw, cout, ge, force_tile=tile, force_split=1, up=up)]), [ref]
+
+    group = [problem(2, 8, 9, 11, 40, 3), problem(1, 16, 5, 7, 136, 1), problem(3, 4, 4, 6, 24, 3)]
+
+    def run_group(tile):
+        with conv.launch_group(True, force_tile=tile):
+            return [conv.conv_forward(xd, wf, ldw, cout, ge) for _, _, xd, wf, ldw, cout, ge in group]
+    return {'plain': single(problem(2, 8, 9, 11, 40, 3)),
+            'up': single(problem(1, 8, 3, 5, 40, 3), up=True),
+            'group': (run_group, [F.conv2d(x, wt, padding=ge.pad) for x, wt, _, _, _, _, ge in group]),
+            'scalar': single(problem(1, 6, 7, 5, 40, 3))}
+
+
+def check_table_walk(device, ids=None):
+    """Every id of the tile-variant table (fsv_conv_tile_info; product library: the knock-out rows of a diagnostic build are wrong
+    by construction) forced through the four dispatchers of csrc/conv_igemm.hip - plain float4 launch, folded up-sampling, grouped
+    launch, scalar gather: each result against F.conv2d at the kernels' 2e-5 and, unless the row loads straight into LDS (mode 2:
+    another order of the fp32 chain), bit-equal to the same unsplit call with the id's shape forced.  ids=None: all of them, then
+    check_table_refusals."""
+    table = tile_table()
+    assert all(table[t[2]][2] == t[2] for t in table.values()), 'every shape is a row that is its own shape'
+    paths = _walk_paths(device)
+    base = {}
+    for tile in sorted(table) if ids is None else ids:
+        shape, mode = table[tile][2], table[tile][5]
+        for name, (run, refs) in paths.items():
+            outs = run(tile)
+            for i, (y, ref) in enumerate(zip(outs, refs)):
+                oc.assert_close('table walk: id %d, %s launch, problem %d' % (tile, name, i), y, ref, 2e-5)
+            if mode != 2:
+                if (name, shape) not in base:
+                    base[name, shape] = [y.cpu() for y in run(shape)]
+                assert all(torch.equal(y.cpu(), b) for y, b in zip(outs, base[name, shape])), (tile, shape, name)
+    if ids is None:
+        check_table_refusals(device, paths)
+
+
+def check_table_refusals(device, paths=None):
+    """an id that is no row - the gaps between the ids and the one past the last - gets FSV_ERR_BAD_ARG from all four dispatchers"""
+    table = tile_table()
+    for tile in [t for t in range(max(table) + 2) if t not in table]:
+        for name, (run, _) in (paths or _walk_paths(device)).items():
+            assert _status(lambda: run(tile)) == -1, 'id %d is no row of the table: the %s launch must refuse it' % (tile, name)
+
+
 def run_all(device):
+    check_table_walk(device)
     check_forward_tiles(device)
     check_per_sample(device)
     check_wgrad_tiles(device)
