@@ -61,8 +61,9 @@ struct SpadeConv3P {
   const float* wscale;    // optional device scalar on the accumulator (spectral-norm 1 / sigma)
   int Cout, ldwc;
   int tiles_x, ntiles;
-  double* stats;          // optional: zeroed partials [stats_slots][Cout][2] = (sum v, sum v^2) of the stored output over all samples -
-  int stats_slots;        // the BatchNorm statistics of the normalisation that follows (layout of ConvP::stats, one group)
+  double* stats;          // optional: zeroed partials [stats_groups][stats_slots][Cout][2] = (sum v, sum v^2) of the stored output - the
+  int stats_slots;        // statistics of the normalisation that follows (layout of ConvP::stats): one group over all samples
+  int stats_groups;       // (BatchNorm), or N groups, one per sample (InstanceNorm: a workgroup's pixels lie in sample z)
 };
 
 // TN2 output column blocks of 32 (Cout = 32 TN2); C = 64
@@ -349,7 +350,8 @@ __global__ __launch_bounds__(256, 2) void fsv_spade_conv3_kernel(SpadeConv3P p) 
       // the two half-waves hold the same 32 channels: fold them, then one fp64 atomic pair per channel and wave (conv_igemm.hip)
       s0 += __shfl_xor(s0, 32); q0 += __shfl_xor(q0, 32);
       if (lk == 0) {
-        double* d = p.stats + ((long long)(tile % p.stats_slots) * p.Cout + co) * 2;
+        const long long grp = p.stats_groups > 1 ? z : 0;
+        double* d = p.stats + ((grp * p.stats_slots + tile % p.stats_slots) * p.Cout + co) * 2;
         atomicAdd(d, (double)s0); atomicAdd(d + 1, (double)q0);
       }
     }
@@ -368,16 +370,17 @@ int fsv_spade_conv3_supported(int C, int Cout, int nmaps) {
 // per map k: maps[k] [N][H W][ch[k]] (ch % 4 == 0), wg[k] / wb[k] K-major [ceil32(ch)][ldw] gamma / beta operands, bg[k] / bb[k] [C],
 // w_bstride / b_bstride per-sample strides in floats (0: shared).  wc = the K-major forward operand of the 3x3 weight
 // ([9 C rows = (tap, ci)][ldwc], fsv_prep_weight mode 0), padding 1, stride 1.  hs (optional) receives the modulated + activated
-// tensor.  stats (optional): fp64 partials [stats_slots][Cout][2] of the stored output's per-channel (sum, sum of squares) over all
-// samples - the BatchNorm statistics of the normalisation that follows, finished by fsv_norm_stats_finish like the gather-GEMM's
-// (fsv_conv_gather_fwd_stats, one group); zeroed here unless stats_prezeroed.
+// tensor.  stats (optional): fp64 partials [stats_groups][stats_slots][Cout][2] of the stored output's per-channel (sum, sum of
+// squares) - the statistics of the normalisation that follows, finished by fsv_norm_stats_finish like the gather-GEMM's
+// (fsv_conv_gather_fwd_stats): stats_groups = 1 sums over all samples (BatchNorm), stats_groups = N keeps one group per sample
+// (InstanceNorm); any other count is FSV_ERR_BAD_ARG.  Zeroed here unless stats_prezeroed.
 // FSV_ERR_UNSUPPORTED for geometries without a kernel (fsv_spade_conv3_supported).
 int fsv_spade_conv3_fwd(const float* x, const float* mean, const float* rstd, float* hs, float* out,
                         int nmaps, const float* const* maps, const float* const* wg, const float* const* wb,
                         const float* const* bg, const float* const* bb, const int* ch, const long long* w_bstride,
                         const long long* b_bstride, int N, int H, int W, int C, int ldw, long long stat_bstride, int up, int act,
                         const float* wc, int ldwc, int Cout, const float* bias, const float* res, const float* wscale,
-                        double* stats, int stats_slots, int stats_prezeroed, hipStream_t stream) {
+                        double* stats, int stats_groups, int stats_slots, int stats_prezeroed, hipStream_t stream) {
   if (!x || !mean || !rstd || !out || !wc || !maps || !wg || !wb || !bg || !bb || !ch || N < 1 || H < 1 || W < 1 || (ldw & 3) ||
       ldwc < Cout || (ldwc & 3))
     return FSV_ERR_BAD_ARG;
@@ -399,11 +402,11 @@ int fsv_spade_conv3_fwd(const float* x, const float* mean, const float* rstd, fl
   p.nmaps = nmaps; p.N = N; p.H = H; p.W = W; p.C = C; p.ldw = ldw; p.stat_bstride = stat_bstride;
   p.up = up ? 1 : 0; p.act = act;
   p.wc = wc; p.bias = bias; p.res = res; p.wscale = wscale; p.Cout = Cout; p.ldwc = ldwc;
-  p.stats = nullptr; p.stats_slots = 1;
+  p.stats = nullptr; p.stats_slots = 1; p.stats_groups = 1;
   if (stats) {
-    if (stats_slots < 1) return FSV_ERR_BAD_ARG;
-    p.stats = stats; p.stats_slots = stats_slots;
-    if (!stats_prezeroed) (void)hipMemsetAsync(stats, 0, (size_t)stats_slots * Cout * 2 * sizeof(double), stream);
+    if (stats_slots < 1 || (stats_groups != 1 && stats_groups != N)) return FSV_ERR_BAD_ARG;
+    p.stats = stats; p.stats_slots = stats_slots; p.stats_groups = stats_groups;
+    if (!stats_prezeroed) (void)hipMemsetAsync(stats, 0, (size_t)stats_groups * stats_slots * Cout * 2 * sizeof(double), stream);
   }
   p.tiles_x = fsv_cdiv(W, 16);
   p.ntiles = p.tiles_x * fsv_cdiv(H, 8);

@@ -111,6 +111,10 @@ class BatchNorm(nn.Module):
 
     MOMENTUM = 0.1
 
+    def stats_hint(self, training):
+        # (the hint only pays when the consumer reduces batch statistics: eval-mode BatchNorm takes its running buffers)
+        return 1 if training else 0
+
     def forward(self, x, act=ACT_NONE):
         self.note_forward()
         return ops.norm_act(x, self.weight if self.affine else None, self.bias if self.affine else None,
@@ -119,15 +123,61 @@ class BatchNorm(nn.Module):
 
 
 class InstanceNorm(nn.Module):
-    """nn.InstanceNorm2d(affine=True, eps=0.1) of the discriminator."""
+    """nn.InstanceNorm2d without running buffers: the discriminator's and get_nonspade_norm_layer's (affine=True, eps=0.1), the
+    parameter-free ones of SPADE (affine=False, eps=0.1) and of generalNorm (affine=False, torch's eps).  The same in eval()."""
 
-    def __init__(self, c):
+    def __init__(self, c, affine=True, eps=0.1):
         super().__init__()
-        self.weight = nn.Parameter(torch.ones(c))
-        self.bias = nn.Parameter(torch.zeros(c))
+        self.affine, self.eps = affine, eps
+        if affine:
+            self.weight = nn.Parameter(torch.ones(c))
+            self.bias = nn.Parameter(torch.zeros(c))
+
+    def stats_hint(self, training):
+        return -1
 
     def forward(self, x, act=ACT_NONE):
-        return ops.norm_act(x, self.weight, self.bias, None, None, instance=True, eps=0.1, act=act, training=True)
+        return ops.norm_act(x, self.weight if self.affine else None, self.bias if self.affine else None, None, None, instance=True,
+                            eps=self.eps, act=act, training=True)
+
+
+NORMS_G = ('spectralspadesyncbatch', 'spectralspadebatch', 'spectralspadeinstance')
+NORMS_F = ('spectralsyncbatch', 'spectralbatch', 'spectralinstance', 'spectralnone')
+
+
+def norm_kind(norm, spade=False):
+    """'batch' / 'instance' / 'none' of a --norm_G (spade=True: generator.py:32, only the SPADE main branch is built here) or of a
+    --norm_F / norm_ref string (normalization.py:64-84)"""
+    if spade:
+        if norm not in NORMS_G:
+            raise NotImplementedError("norm_G = %r: only %s" % (norm, ', '.join(NORMS_G)))
+        norm = norm.replace('spade', '')
+    if norm not in NORMS_F:
+        raise ValueError('normalization layer %s is not recognized' % (norm[len('spectral'):] if str(norm).startswith('spectral')
+                                                                       else norm,))
+    sub = norm[len('spectral'):]
+    return 'batch' if 'batch' in sub else sub
+
+
+def make_norm(norm, c, role):
+    """The normalisation module a norm string stands for, by where it sits:
+      'spade'  SPADE.norm (normalization.py:32-35): parameter-free; InstanceNorm2d(eps=0.1) or the batch norm
+      'plain'  generalNorm's NormalNorm (architecture.py:40-55: SPADEConv2d.bn, the bn_* of a block without SPADE): torch's defaults -
+               affine BatchNorm, or InstanceNorm2d(affine=False, eps=1e-5)
+      'layer'  get_nonspade_norm_layer (normalization.py:77-84): affine BatchNorm / InstanceNorm2d(affine=True, eps=0.1); None for
+               'spectralnone' (the convolution then keeps its bias and stands alone in its slot)"""
+    kind = norm_kind(norm, spade=(role == 'spade'))
+    if role == 'spade':
+        return InstanceNorm(c, affine=False, eps=0.1) if kind == 'instance' else BatchNorm(c, affine=False)
+    if role == 'plain':
+        if kind == 'none':
+            # (the reference fails here too: generalNorm derives NormalNorm from None - `--norm_F spectralnone` needs --n_blocks_F 0)
+            raise TypeError("norm %r names no normalisation class for a residual block (architecture.py:40-55: the reference raises "
+                            "'NoneType takes no arguments'); use --n_blocks_F 0 with it" % (norm,))
+        return InstanceNorm(c, affine=False, eps=1e-5) if kind == 'instance' else BatchNorm(c, affine=True)
+    if kind == 'none':
+        return None
+    return InstanceNorm(c, affine=True, eps=0.1) if kind == 'instance' else BatchNorm(c, affine=True)
 
 
 class _Slot(nn.Module):
@@ -143,22 +193,23 @@ def _seq(*mods):
 
 # ------------------------------------------------------------------------------------------------ building blocks
 class SPADEConv2d(nn.Module):
-    """conv3x3(SN) -> BatchNorm(affine) -> LeakyReLU  (reference architecture.py:57-69 with norm='spectralsyncbatch')."""
+    """conv3x3(SN) -> norm -> LeakyReLU  (reference architecture.py:57-69): affine BatchNorm for norm='spectralsyncbatch' /
+    'spectralbatch', nn.InstanceNorm2d with torch's defaults (no parameters, no buffers) for 'spectralinstance'."""
 
-    def __init__(self, fin, fout, stride=1):
+    def __init__(self, fin, fout, stride=1, norm='spectralsyncbatch'):
         super().__init__()
         self.conv = Conv2d(fin, fout, 3, stride=stride, padding=1, spectral=True)
-        self.bn = BatchNorm(fout, affine=True)
+        self.bn = make_norm(norm, fout, 'plain')
 
     def forward(self, x):
-        # (the hint only pays when the consumer reduces batch statistics: eval-mode BatchNorm takes its running buffers)
-        return self.bn(self.conv(x, stats=1 if self.training else 0), act=ACT_LRELU)
+        return self.bn(self.conv(x, stats=self.bn.stats_hint(self.training)), act=ACT_LRELU)
 
 
 class SPADE(nn.Module):
-    """Reference normalization.py:18-52 (ks = 1 or 3): param-free BatchNorm + sequential (1+gamma)*x+beta per map."""
+    """Reference normalization.py:18-52 (ks = 1 or 3): param-free BatchNorm (or, for a norm with 'instance', InstanceNorm2d with
+    eps = 0.1) + sequential (1+gamma)*x+beta per map."""
 
-    def __init__(self, norm_nc, hidden_nc, params_free=False, ks=1):
+    def __init__(self, norm_nc, hidden_nc, params_free=False, ks=1, norm='spectralspadesyncbatch'):
         super().__init__()
         if not isinstance(hidden_nc, list):
             hidden_nc = [hidden_nc]
@@ -170,8 +221,12 @@ class SPADE(nn.Module):
                 s = str(i + 1) if i > 0 else ''
                 setattr(self, 'mlp_gamma%s' % s, Conv2d(nh, norm_nc, ks, padding=ks // 2))
                 setattr(self, 'mlp_beta%s' % s, Conv2d(nh, norm_nc, ks, padding=ks // 2))
-        self.norm = BatchNorm(norm_nc, affine=False)
+        self.norm = make_norm(norm, norm_nc, 'spade')
+        self.instance = isinstance(self.norm, InstanceNorm)
         self.norm_nc = norm_nc
+
+    def stats_hint(self, training):
+        return self.norm.stats_hint(training)
 
     def forward(self, x, maps, weights=None, act=ACT_NONE, up=False):
         if not isinstance(maps, list):
@@ -194,6 +249,8 @@ class SPADE(nn.Module):
                         lambda: torch.zeros(wg.shape[0], self.norm_nc, dtype=wg.dtype, device=wg.device))
                 use_w.append((wg, wb, zb, zb))
             use_maps.append(m)
+        if self.instance:
+            return ops.spade_mod(x, use_maps, use_w, None, None, act=act, training=True, eps=self.norm.eps, up=up, instance=True)
         self.norm.note_forward()
         return ops.spade_mod(x, use_maps, use_w, self.norm.running_mean, self.norm.running_var, act=act, training=self.training, up=up)
 
@@ -213,8 +270,10 @@ class SPADEResnetBlock(nn.Module):
     """Reference architecture.py:71-108 (SPADE or plain-BatchNorm flavour).  conv_params_free (--adaptive_conv): conv_0, conv_1 and
     conv_s own no parameters and no spectral norm; forward() takes their per-sample [weight, bias] pairs as `conv_weights`."""
 
-    def __init__(self, fin, fout, hidden_nc=0, spade=True, norm_params_free=False, spade_ks=1, conv_params_free=False):
+    def __init__(self, fin, fout, hidden_nc=0, spade=True, norm_params_free=False, spade_ks=1, conv_params_free=False, norm=None):
         super().__init__()
+        if norm is None:
+            norm = 'spectralspadesyncbatch' if spade else 'spectralsyncbatch'
         self.spade_ks = spade_ks
         fhidden = min(fin, fout)
         self.learned_shortcut = fin != fout
@@ -230,15 +289,15 @@ class SPADEResnetBlock(nn.Module):
             if self.learned_shortcut:
                 self.conv_s = Conv2d(fin, fout, 1, bias=False, spectral=True)
         if spade:
-            self.bn_0 = SPADE(fin, hidden_nc, norm_params_free, spade_ks)
-            self.bn_1 = SPADE(fhidden, hidden_nc, norm_params_free, spade_ks)
+            self.bn_0 = SPADE(fin, hidden_nc, norm_params_free, spade_ks, norm)
+            self.bn_1 = SPADE(fhidden, hidden_nc, norm_params_free, spade_ks, norm)
             if self.learned_shortcut:
-                self.bn_s = SPADE(fin, hidden_nc, norm_params_free, spade_ks)
+                self.bn_s = SPADE(fin, hidden_nc, norm_params_free, spade_ks, norm)
         else:
-            self.bn_0 = BatchNorm(fin)
-            self.bn_1 = BatchNorm(fhidden)
+            self.bn_0 = make_norm(norm, fin, 'plain')
+            self.bn_1 = make_norm(norm, fhidden, 'plain')
             if self.learned_shortcut:
-                self.bn_s = BatchNorm(fin)
+                self.bn_s = make_norm(norm, fin, 'plain')
 
     def _conv(self, name, x, wb, **kw):
         m = getattr(self, name)
@@ -253,7 +312,8 @@ class SPADEResnetBlock(nn.Module):
         own launch."""
         nw = norm_weights if norm_weights else [None] * 3
         cw = conv_weights if conv_weights else [None] * 3
-        fold = up and self.spade and self.learned_shortcut and x.shape[1] % 16 == 0 and ops.spade_can_fold_upsample()
+        fold = (up and self.spade and self.learned_shortcut and x.shape[1] % 16 == 0 and
+                ops.spade_can_fold_upsample(instance=self.bn_0.instance))
         if up and not fold:
             x = ops.upsample2x(x)
         if self.spade:
@@ -271,7 +331,8 @@ class SPADEResnetBlock(nn.Module):
             # conv_0 feeds bn_1, conv_1 (+ shortcut) the next block's bn_0 / bn_s: BatchNorm statistics from their epilogues
             # (in training mode only: eval-mode BatchNorm takes its running buffers and would leave the partials unused; a next
             # block that materialises the up-sampling - up and not fold - reduces over the up-sampled tensor itself)
-            hint = 1 if self.training else 0
+            # (an instance norm reduces per sample in eval() too: -1)
+            hint = self.bn_1.stats_hint(self.training)
             if conv3:
                 # round 6, opt-in (FSV_SPADE_CONV3=1): actvn(bn_*) -> 3x3 convolution as ONE kernel where csrc/spade_conv3.hip covers
                 # the widths (the modulated tensor stays in LDS); anything else falls through to the two launches
@@ -282,7 +343,7 @@ class SPADEResnetBlock(nn.Module):
                                       stats=hint if feeds_norm else 0)
             dx = self._conv('conv_0', h0, cw[0], stats=hint)
             return self._conv('conv_1', self.bn_1(dx, label, nw[1], act=ACT_LRELU), cw[1], res=x_s, stats=hint if feeds_norm else 0)
-        hint = 1 if self.training else 0
+        hint = self.bn_1.stats_hint(self.training)
         x_s = self._conv('conv_s', self.bn_s(x), cw[2]) if self.learned_shortcut else x
         dx = self._conv('conv_0', self.bn_0(x, act=ACT_LRELU), cw[0], stats=hint)
         return self._conv('conv_1', self.bn_1(dx, act=ACT_LRELU), cw[1], res=x_s, stats=hint if feeds_norm else 0)
@@ -312,6 +373,9 @@ class LabelEmbedder(nn.Module):
 
     def __init__(self, opt, input_nc, netS, params_free_layers=0):
         super().__init__()
+        # generator.py:510 builds get_nonspade_norm_layer(opt, opt.norm_F) and never applies it: every convolution here is bare
+        # under every --norm_F; the string is only held to the accepted set
+        norm_kind(getattr(opt, 'norm_F', 'spectralsyncbatch'))
         nf = opt.ngf
         self.unet = 'unet' in netS
         self.decode = 'decoder' in netS or self.unet
@@ -392,13 +456,20 @@ class FlowGenerator(nn.Module):
         self.flow_multiplier = opt.flow_multiplier
         ch = _channels(nf, nd + 1)
 
+        norm = getattr(opt, 'norm_F', 'spectralsyncbatch')
+
         def normed(cin, cout, stride=1):
-            return _seq(Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False, spectral=True), BatchNorm(cout))
+            # get_nonspade_norm_layer (normalization.py:62-86): Sequential(sn(conv without bias), norm) - or, for 'spectralnone', the
+            # spectral convolution itself, bias kept, in the same slot
+            layer = make_norm(norm, cout, 'layer')
+            if layer is None:
+                return Conv2d(cin, cout, 3, stride=stride, padding=1, bias=True, spectral=True)
+            return _seq(Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False, spectral=True), layer)
         down = [normed(input_nc, nf), _Slot()]
         for i in range(nd):
             down += [normed(ch[i], ch[i + 1], 2), _Slot()]
         self.down_flow = _seq(*down)
-        self.res_flow = _seq(*[SPADEResnetBlock(ch[nd], ch[nd], spade=False) for _ in range(opt.n_blocks_F)])
+        self.res_flow = _seq(*[SPADEResnetBlock(ch[nd], ch[nd], spade=False, norm=norm) for _ in range(opt.n_blocks_F)])
         up = []
         for i in reversed(range(nd)):
             up += [_Slot(), normed(ch[i + 1], ch[i]), _Slot()]
@@ -406,16 +477,20 @@ class FlowGenerator(nn.Module):
         self.conv_flow = _seq(Conv2d(nf, 2, 3, padding=1))
         self.conv_mask = _seq(Conv2d(nf, 1, 3, padding=1), _Slot())
 
+    def _normed(self, layer, x, up=False):
+        if isinstance(layer, Conv2d):           # 'spectralnone': convolution (+ bias) -> LeakyReLU
+            return layer(x, act=ACT_LRELU, up=up)
+        conv, bn = layer
+        return bn(conv(x, stats=bn.stats_hint(self.training), up=up), act=ACT_LRELU)
+
     def forward(self, label, label_prev, img_prev, for_ref=False):
         x = ops.cat_channels([label, label_prev, img_prev])
         for k in range(0, 2 * (self.nd + 1), 2):
-            conv, bn = self.down_flow[k]
-            x = bn(conv(x, stats=1 if self.training else 0), act=ACT_LRELU)
+            x = self._normed(self.down_flow[k], x)
         for k, blk in enumerate(self.res_flow):
             x = blk(x, feeds_norm=k + 1 < len(self.res_flow))
         for k in range(1, 3 * self.nd, 3):
-            conv, bn = self.up_flow[k]
-            x = bn(conv(x, stats=1 if self.training else 0, up=True), act=ACT_LRELU)           # generator.py:489-493: Upsample -> conv
+            x = self._normed(self.up_flow[k], x, up=True)           # generator.py:489-493: Upsample -> conv
         flow = self.conv_flow[0](x, scale=float(self.flow_multiplier))
         mask = self.conv_mask[0](x, act=ACT_SIGMOID)
         return flow, mask
@@ -459,6 +534,16 @@ class FewShotGenerator(nn.Module):
         exact = str(getattr(opt, 'amp', '') or '').lower() in ('', 'o0', 'fp32', 'f32')
         if (self.concat_label_ref or self.adap_conv) and not exact:
             raise NotImplementedError("use_label_ref = 'concat' / adaptive_conv under --amp (exact fp32 only)")
+        # --norm_G / --norm_F (generator.py:32,62,469): batch or instance statistics in the decoder's SPADE layers and, with 'spade'
+        # dropped (norm_ref), in every SPADEConv2d encoder; the flow network's layers follow norm_F
+        self.norm = norm = getattr(opt, 'norm_G', NORMS_G[0])
+        norm_F = getattr(opt, 'norm_F', NORMS_F[0])
+        norm_kind(norm, spade=True)
+        norm_kind(norm_F)
+        norm_ref = norm.replace('spade', '')
+        if not exact and (norm != NORMS_G[0] or norm_F != NORMS_F[0]):
+            raise NotImplementedError("norm_G = %r / norm_F = %r under --amp (the half-precision SPADE forms reduce batch statistics "
+                                      "only)" % (norm, norm_F))
         if opt.conv_ks != 3:
             raise NotImplementedError("conv_ks = %r: only 3 (the reference hard-codes padding 1 and a 3x3 get_conv_weights)"
                                       % (opt.conv_ks,))
@@ -486,15 +571,15 @@ class FewShotGenerator(nn.Module):
         self.n_fc_layers = opt.n_fc_layers
         input_nc = opt.label_nc if opt.label_nc != 0 else opt.input_nc
         concat = self.concat_label_ref
-        self.ref_img_first = SPADEConv2d(opt.output_nc + (input_nc if concat else 0), nf)
+        self.ref_img_first = SPADEConv2d(opt.output_nc + (input_nc if concat else 0), nf, norm=norm_ref)
         if not concat:
-            self.ref_label_first = SPADEConv2d(input_nc, nf)
+            self.ref_label_first = SPADEConv2d(input_nc, nf, norm=norm_ref)
         for i in range(n):
-            setattr(self, 'ref_img_down_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2))
-            setattr(self, 'ref_img_up_%d' % i, SPADEConv2d(ch[i + 1], ch[i]))
+            setattr(self, 'ref_img_down_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2, norm=norm_ref))
+            setattr(self, 'ref_img_up_%d' % i, SPADEConv2d(ch[i + 1], ch[i], norm=norm_ref))
             if not concat:
-                setattr(self, 'ref_label_down_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2))
-                setattr(self, 'ref_label_up_%d' % i, SPADEConv2d(ch[i + 1], ch[i]))
+                setattr(self, 'ref_label_down_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2, norm=norm_ref))
+                setattr(self, 'ref_label_up_%d' % i, SPADEConv2d(ch[i + 1], ch[i], norm=norm_ref))
         if self.adap_spade or self.adap_conv:
             for i in range(self.n_adaptive_layers):
                 ch_in, ch_out = ch[i], ch[i + 1]
@@ -524,14 +609,14 @@ class FewShotGenerator(nn.Module):
             setattr(self, 'up_%d' % i, SPADEResnetBlock(ch[i + 1], ch[i], hidden_nc=ch_hidden[i], spade=True,
                                                        norm_params_free=(self.adap_spade and i < self.n_adaptive_layers),
                                                        spade_ks=self.spade_ks,
-                                                       conv_params_free=(self.adap_conv and i < self.n_adaptive_layers)))
+                                                       conv_params_free=(self.adap_conv and i < self.n_adaptive_layers), norm=norm))
         self.conv_img = Conv2d(nf, 3, 3, padding=1)
         if self.n_shot > 1:                # generator.py:128-134: key / query encoders of the attention module
-            self.atn_query_first = SPADEConv2d(input_nc, nf)
-            self.atn_key_first = SPADEConv2d(input_nc, nf)
+            self.atn_query_first = SPADEConv2d(input_nc, nf, norm=norm_ref)
+            self.atn_key_first = SPADEConv2d(input_nc, nf, norm=norm_ref)
             for i in range(self.n_downsample_A):
-                setattr(self, 'atn_key_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2))
-                setattr(self, 'atn_query_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2))
+                setattr(self, 'atn_key_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2, norm=norm_ref))
+                setattr(self, 'atn_query_%d' % i, SPADEConv2d(ch[i], ch[i + 1], stride=2, norm=norm_ref))
         self._sn_group, self._sn_count = None, -1
         self.warp_prev = False
         self.warp_ref = opt.warp_ref and not getattr(opt, 'for_face', False)

@@ -1133,14 +1133,14 @@ def _spade_conv_s_launch(site, wt, ldws, cout, wscale, want_hs):
             lib.call("fsv_spade_conv_s_fwd_h", lib.ptr(site['x']), lib.ptr(site['mean']), lib.ptr(site['rstd']),
                      lib.ptr(site['h']) if want_hs else None, lib.ptr(xs), len(chs), _pp(site['maps']), arr(site['wg']),
                      arr(site['wb']), arr(site['bg']), arr(site['bb']), lib.int_array(chs + [0]), _ll(site['wstr'] + [0]),
-                     _ll(site['bstr'] + [0]), n, hw, c, 0, w, up, lib.ptr(wt), ldws, cout, lib.ptr(wscale), lib.stream_ptr())
+                     _ll(site['bstr'] + [0]), n, hw, c, site.get('sbs', 0), w, up, lib.ptr(wt), ldws, cout, lib.ptr(wscale), lib.stream_ptr())
             if _hconv.launch_hook() is not None:
                 _hconv.launch_hook()('spade_conv_s', dict(site=site, wt=wt, cout=cout, wscale=wscale, xs=xs, want_hs=want_hs))
         else:
             lib.call("fsv_spade_conv_s_fwd", lib.ptr(site['x']), lib.ptr(site['mean']), lib.ptr(site['rstd']),
                      lib.ptr(site['h']) if want_hs else None, lib.ptr(xs), len(chs), _pp(site['maps']), arr(site['wg']),
                      arr(site['wb']), arr(site['bg']), arr(site['bb']), lib.int_array(chs + [0]), _ll(site['wstr'] + [0]),
-                     _ll(site['bstr'] + [0]), n, hw, c, ldw, 0, w, up, lib.ptr(wt), ldws, cout, lib.ptr(wscale), lib.stream_ptr())
+                     _ll(site['bstr'] + [0]), n, hw, c, ldw, site.get('sbs', 0), w, up, lib.ptr(wt), ldws, cout, lib.ptr(wscale), lib.stream_ptr())
     return xs
 
 
@@ -1171,7 +1171,8 @@ def _spade_conv3_fits(site, geom, per_sample, res, act, scale, half, cpad, cout,
 
 def _spade_conv3_launch(site, wt, ldwc, cout, wscale, bias, res, want_hs, st=None):
     """out = conv3x3(actvn(bn(x))) (+ bias, + res) in one launch; returns out (NHWC storage, logical NCHW).  st: the statistics hint
-    of conv_forward ({'groups': 1}: a BatchNorm follows) - filled with the epilogue's partials like the gather-GEMM's"""
+    of conv_forward ({'groups': 1}: a BatchNorm follows, {'groups': n}: an InstanceNorm, one group per sample) - filled with the
+    epilogue's partials like the gather-GEMM's"""
     arr = lambda v: (ctypes.c_void_p * max(len(v), 1))(*v)
     n, hw, c, ldw, w, up = site['dims']
     chs = site['chs']
@@ -1181,18 +1182,19 @@ def _spade_conv3_launch(site, wt, ldwc, cout, wscale, bias, res, want_hs, st=Non
         res = to_nhwc(res)
     lib.check_device(site['x'], wt, wscale, bias, res)
     part, prezeroed = None, False
-    if st is not None and int(st['groups']) == 1 and _conv.stats_enabled():
-        part = _conv.stats_arena(out.device).take(_conv.STATS_SLOTS * cout * 2)
+    groups = int(st['groups']) if st is not None else 1
+    if st is not None and groups in (1, n) and _conv.stats_enabled():
+        part = _conv.stats_arena(out.device).take(groups * _conv.STATS_SLOTS * cout * 2)
         prezeroed = part is not None
         if part is None:
-            part = torch.empty(_conv.STATS_SLOTS * cout * 2, dtype=torch.float64, device=out.device)
+            part = torch.empty(groups * _conv.STATS_SLOTS * cout * 2, dtype=torch.float64, device=out.device)
     with profile.scope('fsv_spade_conv3_kernel' + (' P%d C%d N%d K%s' % (n * hw, c, cout, '+'.join(map(str, chs))) if profile.detail() else ''),
                        site['flops'] + 2.0 * n * hw * 9 * c * cout):
         lib.call("fsv_spade_conv3_fwd", lib.ptr(site['x']), lib.ptr(site['mean']), lib.ptr(site['rstd']),
                  lib.ptr(site['h']) if want_hs else None, lib.ptr(out), len(chs), _pp(site['maps']), arr(site['wg']),
                  arr(site['wb']), arr(site['bg']), arr(site['bb']), lib.int_array(chs + [0]), _ll(site['wstr'] + [0]),
-                 _ll(site['bstr'] + [0]), n, hgt, w, c, ldw, 0, up, site['act'], lib.ptr(wt), ldwc, cout, lib.ptr(bias),
-                 lib.ptr(res), lib.ptr(wscale), lib.ptr(part), _conv.STATS_SLOTS, 1 if prezeroed else 0, lib.stream_ptr())
+                 _ll(site['bstr'] + [0]), n, hgt, w, c, ldw, site.get('sbs', 0), up, site['act'], lib.ptr(wt), ldwc, cout, lib.ptr(bias),
+                 lib.ptr(res), lib.ptr(wscale), lib.ptr(part), groups, _conv.STATS_SLOTS, 1 if prezeroed else 0, lib.stream_ptr())
     if part is not None:
         st['part'], st['slots'] = part, _conv.STATS_SLOTS
     return out
@@ -1221,14 +1223,14 @@ def _spade_launch(a):
         if a.get('half'):
             lib.call("fsv_spade_mod_fwd_h", lib.ptr(a['x']), lib.ptr(a['mean']), lib.ptr(a['rstd']), lib.ptr(a['h']), len(chs),
                      _pp(a['maps']), arr(a['wg']), arr(a['wb']), arr(a['bg']), arr(a['bb']), lib.int_array(chs + [0]),
-                     _ll(a['wstr'] + [0]), _ll(a['bstr'] + [0]), n, hw, c, ldw, 0, a['act'], w, up,
+                     _ll(a['wstr'] + [0]), _ll(a['bstr'] + [0]), n, hw, c, ldw, a.get('sbs', 0), a['act'], w, up,
                      1 | (4 if a.get('f16') else 0), lib.stream_ptr())
             if _hconv.launch_hook() is not None:
                 _hconv.launch_hook()('spade_fwd', dict(site=a))
         else:
             lib.call("fsv_spade_mod_fwd", lib.ptr(a['x']), lib.ptr(a['mean']), lib.ptr(a['rstd']), lib.ptr(a['h']), len(chs),
                      _pp(a['maps']), arr(a['wg']), arr(a['wb']), arr(a['bg']), arr(a['bb']), lib.int_array(chs + [0]),
-                     _ll(a['wstr'] + [0]), _ll(a['bstr'] + [0]), n, hw, c, ldw, 0, a['act'], w, up, lib.stream_ptr())
+                     _ll(a['wstr'] + [0]), _ll(a['bstr'] + [0]), n, hw, c, ldw, a.get('sbs', 0), a['act'], w, up, lib.stream_ptr())
 
 
 class _SpadeFn(torch.autograd.Function):
@@ -1243,9 +1245,12 @@ class _SpadeFn(torch.autograd.Function):
         # act may be (act, up): up = 1 -> x is the HALF-resolution tensor; the kernels read it through the nearest x2
         # up-sampling index (generator.py:124 folded into SPADE: the up-sampled tensor is never written) and the statistics
         # are those of x with every value counted four times
-        up = 0
+        # ... or (act, up, instance): instance = 1 -> the statistics are per (sample, channel) over H W (nn.InstanceNorm2d without
+        # affine parameters or running buffers, normalization.py:35): mean / rstd are [N][C], every kernel indexes them by sample
+        # (stat_bstride = C), the backward reduces per sample, and eval() changes nothing
+        up, inst = 0, 0
         if isinstance(act, tuple):
-            act, up = act
+            act, up, inst = (tuple(act) + (0,))[:3]
         x_arg = x
         x = to_nhwc(x)
         n, c, h, w = x.shape
@@ -1258,7 +1263,15 @@ class _SpadeFn(torch.autograd.Function):
         wbs = [rest[5 * k + 2] for k in range(nmaps)]
         bgs = [rest[5 * k + 3] for k in range(nmaps)]
         bbs = [rest[5 * k + 4] for k in range(nmaps)]
-        if training or run_mean is None:
+        ctx.inst = bool(inst)
+        # statistics groups / pixels per group / per-sample stride of mean and rstd in the kernels
+        ctx.sg, ctx.sp, sbs = (n, xs_h * xs_w, c) if inst else (1, n * xs_h * xs_w, 0)
+        ctx.sbs = sbs
+        if inst:
+            got = _stats_from_producer(x_arg, n, xs_h * xs_w, c, eps, None, None, momentum, rep=4 if up else 1)
+            mean, rstd = got if got is not None else norm_stats(x, n, xs_h * xs_w, c, eps, None, None, momentum,
+                                                                rep=4 if up else 1, instance=True)
+        elif training or run_mean is None:
             got = _stats_from_producer(x_arg, 1, n * xs_h * xs_w, c, eps, run_mean, run_var, momentum, rep=4 if up else 1)
             mean, rstd = got if got is not None else norm_stats(x, 1, n * xs_h * xs_w, c, eps, run_mean, run_var, momentum,
                                                                 rep=4 if up else 1)
@@ -1281,6 +1294,8 @@ class _SpadeFn(torch.autograd.Function):
         # a SPADEResnetBlock, architecture.py:92-99) that would round it to half anyway - the kernel rounds at the store and the
         # fp32 tensor + conversion pass disappear; its gradient then arrives as half (the convolutions' data gradient) and the
         # backward twin reads it as such
+        if inst and _conv.h_kernels():
+            raise NotImplementedError("instance-normalised SPADE under --amp (the half-precision forms reduce batch statistics only)")
         ctx.half_out = bool(_conv.h_kernels() and ctx.fast and _os.environ.get('FSV_SPADE_FUSED_BWD', '1') == '1' and nmaps > 0)
         hout = _hconv.empty_nhwc_h(n, c, h, w, x) if ctx.half_out else empty_nhwc(n, c, h, w, x)
         # ... and the gamma / beta GEMMs themselves on the f16 matrix instructions: half label maps (one conversion per map tensor,
@@ -1360,7 +1375,7 @@ class _SpadeFn(torch.autograd.Function):
                 bstr.append(2 * c if per_sample else 0)
             site = dict(x=x, mean=mean, rstd=rstd, h=hout, maps=maps, wg=wg_p, wb=wb_p, bg=bg_p, bb=bb_p, chs=chs, wstr=wstr,
                         bstr=bstr, dims=(n, h * w, c, ldw, w, up), act=act, keep=prepped, half=ctx.half_out, f16=ctx.f16,
-                        flops=2.0 * n * h * w * c * 2 * sum(chs))
+                        sbs=sbs, flops=2.0 * n * h * w * c * 2 * sum(chs))
             defer = getattr(_spade_tls, 'defer', None)
             conv3 = bool(defer is not None and defer.conv3)
             if (defer is not None and defer.pending is None and nmaps > 0 and
@@ -1371,8 +1386,8 @@ class _SpadeFn(torch.autograd.Function):
             else:
                 _spade_launch(site)
             ctx.nmaps, ctx.act = nmaps, act
-            ctx.batch_stats = bool(training or run_mean is None)
-            ctx.world = bn_sync_world(1) if ctx.batch_stats else 1
+            ctx.batch_stats = bool(inst or training or run_mean is None)
+            ctx.world = bn_sync_world(ctx.sg, ctx.inst) if ctx.batch_stats else 1
             ctx.per_sample = [wgs[k].dim() == 5 for k in range(nmaps)]
             ctx.w_shapes = [tuple(wgs[k].shape) for k in range(nmaps)]
             ctx.save_for_backward(x, hout, mean, rstd, *maps, *prepped)
@@ -1390,10 +1405,10 @@ class _SpadeFn(torch.autograd.Function):
         with profile.scope('fsv_spade_mod_kernel', 2.0 * n * h * w * c * 2 * sum(chs)):
             lib.call("fsv_spade_mod_fwd", lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(hout), nmaps, _pp(maps),
                      _pp(wg_t), _pp(wb_t), _pp(bg_c), _pp(bb_c), lib.int_array(chs + [0]), _ll(wbs_stride + [0]),
-                     _ll(bbs_stride + [0]), n, h * w, c, ldw, 0, act, w, up, lib.stream_ptr())
+                     _ll(bbs_stride + [0]), n, h * w, c, ldw, sbs, act, w, up, lib.stream_ptr())
         ctx.nmaps, ctx.act = nmaps, act
-        ctx.batch_stats = bool(training or run_mean is None)
-        ctx.world = bn_sync_world(1) if ctx.batch_stats else 1
+        ctx.batch_stats = bool(inst or training or run_mean is None)
+        ctx.world = bn_sync_world(ctx.sg, ctx.inst) if ctx.batch_stats else 1
         ctx.save_for_backward(x, hout, mean, rstd, *maps, *wgs, *wbs, *bgs, *bbs)
         return hout
 
@@ -1432,12 +1447,12 @@ class _SpadeFn(torch.autograd.Function):
                            2.0 * n * h * w * 2 * c * 9 * sum(chs)):
             lib.call("fsv_spade_k3_fwd", lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(hout), nmaps, _pp(maps), _pp(wts),
                      _pp(bcats), lib.int_array(chs + [0]), _ll(wstr + [0]), _ll(bstr + [0]), _pp(gbs) if keep else None,
-                     n, h, w, c, ldw, 0, act, up, lib.stream_ptr())
+                     n, h, w, c, ldw, ctx.sbs, act, up, lib.stream_ptr())
         ctx.k3 = True
         ctx.fast = False
         ctx.nmaps, ctx.act = nmaps, act
-        ctx.batch_stats = bool(training or run_mean is None)
-        ctx.world = bn_sync_world(1) if ctx.batch_stats else 1
+        ctx.batch_stats = bool(ctx.inst or training or run_mean is None)
+        ctx.world = bn_sync_world(ctx.sg, ctx.inst) if ctx.batch_stats else 1
         ctx.per_sample = [wg.dim() == 5 for wg in wgs]
         ctx.save_for_backward(x, hout, mean, rstd, *maps, *wcats, *wts, *bcats, *gbs)
         return hout
@@ -1467,7 +1482,7 @@ class _SpadeFn(torch.autograd.Function):
         dgbs = [empty_nhwc(n, 2 * c, h, w, x) for _ in range(nm)]
         lib.check_device(x, dh, hout, *gbs)
         lib.call("fsv_spade_bwd_elem", lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(dh), lib.ptr(hout), nm,
-                 _pp(gbs), _pp(dgbs), lib.ptr(dxhat), n, h * w, c, 0, ctx.act, w, up, lib.stream_ptr())
+                 _pp(gbs), _pp(dgbs), lib.ptr(dxhat), n, h * w, c, ctx.sbs, ctx.act, w, up, lib.stream_ptr())
         dx = _SpadeFn._dx_from_dxhat(ctx, dxhat, x, mean, rstd, up)
         grads = []
         for k in range(nm):
@@ -1494,7 +1509,8 @@ class _SpadeFn(torch.autograd.Function):
             lib.call("fsv_upsample2x_bwd", lib.ptr(dxhat), lib.ptr(pooled), n, xs_h, xs_w, c, lib.stream_ptr())
             dxhat = pooled
         if ctx.batch_stats:
-            dx, _, _ = bn_backward(dxhat, None, x, mean, rstd, None, 1, n * xs_h * xs_w, c, ACT_NONE, False, False, ctx.world)
+            # (instance statistics: the same reduction per sample - G = N groups of H W pixels)
+            dx, _, _ = bn_backward(dxhat, None, x, mean, rstd, None, ctx.sg, ctx.sp, c, ACT_NONE, False, False, ctx.world)
             return dx
         return dxhat * rstd.view(1, c, 1, 1)
 
@@ -1553,7 +1569,7 @@ class _SpadeFn(torch.autograd.Function):
                     flags = (1 if dh.dtype == torch.float16 else 0) | (6 if f16 else 0)
                     lib.call("fsv_spade_mod_bwd_h", lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(dh), nm, _pp(maps), arr(wg_p),
                              arr(wb_p), arr(bg_p), arr(bb_p), lib.int_array(chs + [0]), _ll(wstr + [0]), _ll(bstr + [0]),
-                             _pp(dgbs), lib.ptr(dxhat), n, h * w, c, 2 * c, 0, ctx.act, w, up, flags,
+                             _pp(dgbs), lib.ptr(dxhat), n, h * w, c, 2 * c, ctx.sbs, ctx.act, w, up, flags,
                              lib.ptr(dbsum) if dbsum is not None else None, _ll(zstr + [0]) if dbsum is not None else None,
                              slots if dbsum is not None else 1, n * nm * 2 * c, lib.stream_ptr())
                     if dbsum is not None:
@@ -1565,7 +1581,7 @@ class _SpadeFn(torch.autograd.Function):
                 else:
                     lib.call("fsv_spade_mod_bwd", lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(dh), nm, _pp(maps), arr(wg_p),
                              arr(wb_p), arr(bg_p), arr(bb_p), lib.int_array(chs + [0]), _ll(wstr + [0]), _ll(bstr + [0]),
-                             _pp(dgbs), lib.ptr(dxhat), n, h * w, c, 2 * c, 0, ctx.act, w, up, lib.stream_ptr())
+                             _pp(dgbs), lib.ptr(dxhat), n, h * w, c, 2 * c, ctx.sbs, ctx.act, w, up, lib.stream_ptr())
         else:
             if fast:
                 prepped = saved[4 + nm:]
@@ -1588,21 +1604,11 @@ class _SpadeFn(torch.autograd.Function):
             # 2) elementwise chain backward
             dgbs = [torch.empty_like(gb) for gb in gbs]
             lib.call("fsv_spade_bwd_elem", lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(dh), lib.ptr(hout), nm,
-                     _pp(gbs), _pp(dgbs), lib.ptr(dxhat), n, h * w, c, 0, ctx.act, w, up, lib.stream_ptr())
+                     _pp(gbs), _pp(dgbs), lib.ptr(dxhat), n, h * w, c, ctx.sbs, ctx.act, w, up, lib.stream_ptr())
         # 3) param-free BatchNorm backward.  With the up-sampling folded in, xhat of the four children of a source pixel
         # is the same value, so with dxhat summed over the children the backward is exactly the BatchNorm backward of
         # the half-resolution tensor (s1 = sum dxhat, s2 = sum dxhat * xhat, count = source pixels).
-        dx = None
-        if ctx.needs_input_grad[4]:
-            if up:
-                pooled = empty_nhwc(n, c, xs_h, xs_w, dxhat)
-                lib.call("fsv_upsample2x_bwd", lib.ptr(dxhat), lib.ptr(pooled), n, xs_h, xs_w, c, lib.stream_ptr())
-                dxhat = pooled
-            if ctx.batch_stats:
-                dx, _, _ = bn_backward(dxhat, None, x, mean, rstd, None, 1, n * xs_h * xs_w, c, ACT_NONE, False, False,
-                                       ctx.world)
-            else:
-                dx = dxhat * rstd.view(1, c, 1, 1)
+        dx = _SpadeFn._dx_from_dxhat(ctx, dxhat, x, mean, rstd, up)
         grads = []
         for k in range(nm):
             per_sample = ctx.per_sample[k] if fast else wgs[k].dim() == 5
@@ -1641,19 +1647,25 @@ class _SpadeFn(torch.autograd.Function):
         return (None, None, None, None, dx, None, None, *grads)
 
 
-def spade_mod(x, maps, weights, run_mean=None, run_var=None, act=ACT_LRELU, training=True, eps=1e-5, momentum=0.1, up=False):
+def spade_mod(x, maps, weights, run_mean=None, run_var=None, act=ACT_LRELU, training=True, eps=1e-5, momentum=0.1, up=False,
+              instance=False):
     """maps: list of tensors; weights: list of (wg, wb, bg, bb) per map (see _SpadeFn).  up=True: x is at half the
-    resolution of the maps and stands for its nearest x2 up-sampling (never materialised)."""
+    resolution of the maps and stands for its nearest x2 up-sampling (never materialised).  instance=True: the normalisation is
+    nn.InstanceNorm2d(affine=False, eps) - statistics per (sample, channel), biased variance, no running buffers (run_mean / run_var
+    are ignored), the same in eval()."""
     flat = []
     for m, (wg, wb, bg, bb) in zip(maps, weights):
         flat += [m, wg, wb, bg, bb]
     _note_grad_mode()
+    if instance:
+        return _SpadeFn.apply((act, 1 if up else 0, 1), True, eps, momentum, x, None, None, *flat)
     return _SpadeFn.apply((act, 1) if up else act, training, eps, momentum, x, run_mean, run_var, *flat)
 
 
-def spade_can_fold_upsample():
-    """the folded form needs per-replica statistics (the cross-replica path exchanges sums of the materialised tensor)"""
-    return bn_sync_world(1) == 1 and _os.environ.get('FSV_SPADE_FOLD', '1') == '1'            # env: in-box A/B switch
+def spade_can_fold_upsample(instance=False):
+    """the folded form needs per-replica statistics (the cross-replica path exchanges sums of the materialised tensor; instance
+    statistics never cross replicas)"""
+    return bn_sync_world(1, instance) == 1 and _os.environ.get('FSV_SPADE_FOLD', '1') == '1'            # env: in-box A/B switch
 
 
 # ------------------------------------------------------------------------------------------------ upsample
