@@ -157,10 +157,11 @@ class Geom:
         return ((h + 2 * self.pad - self.kh) // self.stride + 1, (w + 2 * self.pad - self.kw) // self.stride + 1)
 
 
-def prep_weight(w, mode, geom, khs=None, kws=None, scale=None, out=None):
+def prep_weight(w, mode, geom, khs=None, kws=None, scale=None, out=None, col_scale=None):
     """OIHW weights (optionally a leading per-sample batch dim) -> K-major GEMM operand.
 
     mode 0: forward  wt[(tap, ci)][co];  mode 1: dgrad  wt[(tap, co)][ci].  Returns (wt, Kpad, ldw).
+    col_scale (mode 0, no `scale`): Cout device factors multiplied into the columns (infer.py: a folded eval-mode BatchNorm).
     """
     batched = w.dim() == 5
     nb = w.shape[0] if batched else 1
@@ -178,14 +179,16 @@ def prep_weight(w, mode, geom, khs=None, kws=None, scale=None, out=None):
         w_bstride = w.stride(0)
     else:
         w = w.contiguous()
-    lib.check_device(w, scale)
+    lib.check_device(w, scale, col_scale)
+    if col_scale is not None and (col_scale.numel() != cout or not col_scale.is_contiguous()):
+        raise ValueError("col_scale needs %d contiguous factors" % cout)
     if out is None:
         out = torch.empty((nb, kpad, ldw), dtype=torch.float32, device=w.device)
     if ntaps == 0:
         out.zero_()
         return out, kpad, ldw
     lib.call("fsv_prep_weight", lib.ptr(w), lib.ptr(out), lib.ptr(scale), mode, nb, cout, cin, kh, kw, ntaps,
-             lib.int_array(khs), lib.int_array(kws), kpad, ldw, w_bstride, kpad * ldw, lib.stream_ptr())
+             lib.int_array(khs), lib.int_array(kws), kpad, ldw, w_bstride, kpad * ldw, lib.ptr(col_scale), lib.stream_ptr())
     return out, kpad, ldw
 
 
@@ -199,7 +202,7 @@ def unprep_weight_grad(dwt, w_shape, geom, scale=None, out=None):
     kpad, ldw = dwt.shape[-2], dwt.shape[-1]
     lib.call("fsv_prep_weight", lib.ptr(dw), lib.ptr(dwt), lib.ptr(scale), 3 if out is not None else 2, nb, cout, cin, kh, kw, geom.ntaps,
              lib.int_array(geom.khs), lib.int_array(geom.kws), kpad, ldw, cout * cin * kh * kw, kpad * ldw,
-             lib.stream_ptr())
+             None, lib.stream_ptr())
     return dw
 
 

@@ -24,6 +24,10 @@
 // The weight gradient reduces over pixels, so both of its operands arrive with the reduction index as the slow HBM index and are
 // transposed on the way into LDS through registers (packed pixel pairs, 4-byte transposing stores: conflict free); its LDS-write
 // bound loop is described at the kernel.
+//
+// The dense element conversions live here too (fsv_cast_half): dir 0 fp32 -> half, dir 1 half -> fp32, and dir 2 fp32 -> uint8 - a
+// generated NHWC image in [-1, 1] as the bytes a video encoder takes, with the arithmetic of the reference's tensor2im
+// (util/util.py:61-70: (x + 1) / 2 * 255 in fp32, clipped to [0, 255], truncated; bit-exact against numpy under -ffp-contract=off).
 #include <stdlib.h>
 #include "conv_igemm.h"
 
@@ -787,6 +791,25 @@ __global__ __launch_bounds__(256) void fsv_cast_h2f_kernel(const fsv_h16* x, flo
   for (long long e = (n4 << 2) + i; e < n; e += stride) y[e] = (float)x[e];
 }
 
+// fp32 image in [-1, 1] -> uint8, the reference's tensor2im (util/util.py:61-70, normalised form) op by op in fp32:
+// (x + 1) / 2 * 255, clipped to [0, 255], truncated.  Four pixels' bytes leave as one packed 32-bit vector store.
+__device__ __forceinline__ unsigned fsv_u8_of(float x) {
+  float v = (x + 1.0f) / 2.0f * 255.0f;
+  v = v < 0.0f ? 0.0f : v;
+  v = v > 255.0f ? 255.0f : v;
+  return (unsigned)(int)v;
+}
+__global__ __launch_bounds__(256) void fsv_cast_f2u8_kernel(const float* x, unsigned char* y, long long n) {
+  const long long n4 = n >> 2;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long q = i; q < n4; q += stride) {
+    const float4 v = reinterpret_cast<const float4*>(x)[q];
+    reinterpret_cast<unsigned*>(y)[q] = fsv_u8_of(v.x) | (fsv_u8_of(v.y) << 8) | (fsv_u8_of(v.z) << 16) | (fsv_u8_of(v.w) << 24);
+  }
+  for (long long e = (n4 << 2) + i; e < n; e += stride) y[e] = (unsigned char)fsv_u8_of(x[e]);
+}
+
 // =============================================== host side ===================================================
 static inline void fsv_h_pack_taps(const int* ty, const int* tx, int n, unsigned long long& lo, unsigned long long& hi) {
   lo = 0; hi = 0;
@@ -1097,15 +1120,16 @@ int fsv_hconv_prep_weight_one(const float* src, void* dst, int Kpad32, int ldw, 
   return fsv_check_launch();
 }
 
-// dense element conversion: dir 0 = fp32 -> half, 1 = half -> fp32
+// dense element conversion: dir 0 = fp32 -> half, 1 = half -> fp32, 2 = fp32 image in [-1, 1] -> uint8 (y = n bytes)
 int fsv_cast_half(const void* x, void* y, long long n, int dir, hipStream_t stream) {
-  if (!x || !y || n < 0) return FSV_ERR_BAD_ARG;
+  if (!x || !y || n < 0 || dir < 0 || dir > 2) return FSV_ERR_BAD_ARG;
   if (n == 0) return FSV_OK;
   long long g = (n / 4 + 255) / 256;
   if (g > 8192) g = 8192;
   if (g < 1) g = 1;
   if (dir == 0) FSV_LAUNCH(fsv_cast_f2h_kernel, dim3((unsigned)g), dim3(256), stream, (const float*)x, (fsv_h16*)y, n);
-  else FSV_LAUNCH(fsv_cast_h2f_kernel, dim3((unsigned)g), dim3(256), stream, (const fsv_h16*)x, (float*)y, n);
+  else if (dir == 1) FSV_LAUNCH(fsv_cast_h2f_kernel, dim3((unsigned)g), dim3(256), stream, (const fsv_h16*)x, (float*)y, n);
+  else FSV_LAUNCH(fsv_cast_f2u8_kernel, dim3((unsigned)g), dim3(256), stream, (const float*)x, (unsigned char*)y, n);
   return fsv_check_launch();
 }
 

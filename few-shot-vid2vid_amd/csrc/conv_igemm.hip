@@ -1418,7 +1418,9 @@ static inline bool fsv_conv_thin(int Mz, int K) {
 // mode 2 (inverse of mode 0, for gradients): w[z][co][ci][kh_j][kw_j] = s * wt[z][j*Cin + ci][co]
 // mode 3: as mode 2 but accumulating (+=) - gradients written straight into a flat optimiser buffer
 // taps: (kh | kw<<4) per tap.  Rows >= K and columns >= ncols of wt are written as zero (modes 0/1).
+// col_scale (mode 0, no scale_ptr): wt[z][j*Cin + ci][co] = w[z][co][ci][kh_j][kw_j] * col_scale[co] - one fp32 multiply per weight.
 __global__ __launch_bounds__(256) void fsv_prep_weight_kernel(const float* w, float* wt, const float* scale_ptr,
+                                                              const float* col_scale,
                                                               int mode_in, int Cout, int Cin, int KH, int KW,
                                                               int ntaps, unsigned long long taps_lo,
                                                               unsigned long long taps_hi, int Kpad, int ldw,
@@ -1449,7 +1451,9 @@ __global__ __launch_bounds__(256) void fsv_prep_weight_kernel(const float* w, fl
         ((float*)w)[widx] = accum ? ((float*)w)[widx] + g : g;
       }
     } else {
-      wt[(long long)z * wt_bstride + i] = ok ? s * w[widx] : 0.f;
+      float v = 0.f;
+      if (ok) v = col_scale ? w[widx] * col_scale[co] : s * w[widx];
+      wt[(long long)z * wt_bstride + i] = v;
     }
   }
 }
@@ -2144,15 +2148,16 @@ int fsv_conv_wgrad(const float* in, const float* dout, float* dwt,
 
 int fsv_prep_weight(const float* w, float* wt, const float* scale_ptr, int mode, int nbatch,
                     int Cout, int Cin, int KH, int KW, int ntaps, const int* kh, const int* kw,
-                    int Kpad, int ldw, long long w_bstride, long long wt_bstride, hipStream_t stream) {
+                    int Kpad, int ldw, long long w_bstride, long long wt_bstride, const float* col_scale, hipStream_t stream) {
   if (!w || !wt || ntaps < 1 || ntaps > 16 || mode < 0 || mode > 3) return FSV_ERR_BAD_ARG;
+  if (col_scale && (scale_ptr || mode != 0)) return FSV_ERR_BAD_ARG;
   unsigned long long lo, hi;
   fsv_pack_taps(kh, kw, ntaps, lo, hi, 0);
   long long total = (long long)Kpad * ldw;
   int grid = (int)((total + 255) / 256);
   if (grid > 2048) grid = 2048;
-  FSV_LAUNCH(fsv_prep_weight_kernel, dim3(grid, 1, nbatch), dim3(256), stream, w, wt, scale_ptr, mode, Cout, Cin,
-             KH, KW, ntaps, lo, hi, Kpad, ldw, w_bstride, wt_bstride);
+  FSV_LAUNCH(fsv_prep_weight_kernel, dim3(grid, 1, nbatch), dim3(256), stream, w, wt, scale_ptr, col_scale, mode, Cout,
+             Cin, KH, KW, ntaps, lo, hi, Kpad, ldw, w_bstride, wt_bstride);
   return fsv_check_launch();
 }
 

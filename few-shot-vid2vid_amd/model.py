@@ -821,11 +821,33 @@ class Vid2VidModel(nn.Module):
         if mode == 'discriminator':
             early = self._data_key(data_list) if (self.early_generator and self.isTrain and torch.is_grad_enabled()) else None
             return self.forward_discriminator(tgt_label, tgt_image, ref_label, ref_image, prevs, early=early)
+        sess = self._infer_session
+        if sess is not None:               # use_inference_session(True): frozen weights, one replayed graph per frame (infer.py)
+            return sess(tgt_label, ref_label, ref_image)
         return self.inference(tgt_label, ref_label, ref_image)
+
+    # ---- frozen-weight inference (infer.py): opt-in, the default path above is untouched
+    _infer_session = None
+
+    def inference_session(self, **kw):
+        """an infer.InferenceSession over this model (fold_norms=False, frames_u8=False, warmup=1); the caller drives it"""
+        from . import infer
+        return infer.InferenceSession(self, self.opt, **kw)
+
+    def use_inference_session(self, on=True, **kw):
+        """route `forward(mode='inference')` - the call of the reference's test.py loop - through an InferenceSession (on=False:
+        close it, back to the eager path).  Returns the session."""
+        if self._infer_session is not None:
+            self._infer_session.close()
+            self._infer_session = None
+        if on:
+            self._infer_session = self.inference_session(**kw)
+        return self._infer_session
 
     def inference(self, tgt_label, ref_labels, ref_images):
         """vid2vid_model.py:179-205 (test.py:39-41): one frame per call, previous labels / outputs carried in self.prevs;
-        call reset_inference() between sequences.  --finetune and --refine_face are not part of this build."""
+        call reset_inference() between sequences.  --finetune (test-time adaptation on the references, frame 0) and --refine_face
+        are honoured as in the reference."""
         opt = self.opt
         if getattr(self, 'prevs', None) is None:
             self.prevs = [None, None]

@@ -30,12 +30,15 @@ class _SpectralMixin:
         self.register_buffer('weight_v', F.normalize(torch.randn(cols), dim=0, eps=1e-12))
 
     _sig_cached = None
+    _sig_frozen = None                   # (sigma, 1 / sigma) taken once by an infer.InferenceSession: eval() only, until it refreezes
 
     def _sn(self):
         cached = self._sig_cached        # (sigma pair, u snapshot, v snapshot) from the network-level batched pass
         if cached is not None:
             self._sig_cached = None
             return (cached[0], cached[1], cached[2], True)
+        if self._sig_frozen is not None and not self.training:
+            return (self._sig_frozen, self.weight_u, self.weight_v, False)
         sig = ops.SpectralState.update(self.weight_orig, self.weight_u, self.weight_v, self.training)
         return (sig, self.weight_u, self.weight_v, False)
 
@@ -55,10 +58,23 @@ class Conv2d(nn.Module, _SpectralMixin):
             self.weight = nn.Parameter(w)
         self.bias = nn.Parameter(torch.zeros(cout)) if bias else None
 
+    # infer.InferenceSession(fold_norms=True): (shift vector t, the eval-mode BatchNorm that reads this layer's output and nothing
+    # else).  The frozen layout of the weight then carries gamma * rstd / sigma in its columns, and this launch is
+    # LeakyReLU(conv + t): the BatchNorm finds its own mark on the tensor and hands it on.
+    _fsv_fold = None
+
     def forward(self, x, act=ACT_NONE, res=None, scale=1.0, stats=0, up=False):
         """stats: 1 / -1 when a BatchNorm / InstanceNorm consumes the output next (ops.conv2d stats_groups: the statistics then
         come out of this launch's epilogue instead of a read pass over the output).  up: the convolution of the nearest x2
         up-sampling of x (nn.Upsample in front of this layer in the reference: ops.conv2d folds it into the gather)"""
+        fold = self._fsv_fold
+        if fold is not None and not self.training and not torch.is_grad_enabled():
+            if act != ACT_NONE or res is not None or scale != 1.0:
+                raise ValueError("a convolution with a folded BatchNorm is called with an epilogue of its own")
+            y = ops.conv2d(x, self.weight_orig if self.spectral else self.weight, fold[0], self.stride, self.padding, ACT_LRELU,
+                           1.0, None, None, 0, up)
+            y._fsv_folded_bn = fold[1]
+            return y
         if self.spectral:
             return ops.conv2d(x, self.weight_orig, self.bias, self.stride, self.padding, act, scale, res, self._sn(), stats, up)
         return ops.conv2d(x, self.weight, self.bias, self.stride, self.padding, act, scale, res, None, stats, up)
@@ -116,6 +132,10 @@ class BatchNorm(nn.Module):
         return 1 if training else 0
 
     def forward(self, x, act=ACT_NONE):
+        if getattr(x, '_fsv_folded_bn', None) is self:          # (Conv2d._fsv_fold: the producer already applied this layer)
+            if act != ACT_LRELU or self.training:
+                raise ValueError("a folded BatchNorm is LeakyReLU(eval-mode affine norm) only")
+            return x
         self.note_forward()
         return ops.norm_act(x, self.weight if self.affine else None, self.bias if self.affine else None,
                             self.running_mean, self.running_var, instance=False, eps=1e-5, momentum=BatchNorm.MOMENTUM, act=act,
@@ -832,7 +852,13 @@ class FewShotGenerator(nn.Module):
         # generator.py:370,403-416: at test time (isTrain False, one reference) the generated weights of frame 0 are kept
         # and every later frame only runs the down path of the reference encoder
         fresh = bool(self.opt.isTrain) or n > 1 or t == 0
-        x, enc = self.reference_encoding(img_ref, label_ref, encode=fresh, label=label)
+        kept_x = getattr(self, '_frozen_x', None) if not fresh else None
+        if kept_x is not None:
+            # an infer.InferenceSession keeps frame 0's deepest reference feature with the generated weights: with one reference
+            # and frozen weights the encoder's down path gives the same tensor on every frame
+            x, enc, self._atn = kept_x, None, (None, None)
+        else:
+            x, enc = self.reference_encoding(img_ref, label_ref, encode=fresh, label=label)
         cut2 = getattr(self, 'bwd_cut2', None)
         if cut2 is not None and fresh and torch.is_grad_enabled():
             # second stage boundary (three-piece backward): what the reference encoders hand on - the deepest feature map and
@@ -856,6 +882,7 @@ class FewShotGenerator(nn.Module):
                         conv_w.append(self.get_conv_weights(conv_feats[i], i, fc))
             if not self.opt.isTrain:
                 self._cached_weights = (embed_w, norm_w, conv_w)         # generator.py:415-416
+                self._cached_x = x
         else:
             embed_w, norm_w, conv_w = self._cached_weights
         embed_w = embed_w if self.adap_embed else None

@@ -142,6 +142,23 @@ def colsum(x2d_nhwc, groups, pixels, channels, out=None):
     return out
 
 
+def image_u8(x):
+    """fp32 image in [-1, 1] -> uint8 with the arithmetic of the reference's tensor2im (util/util.py:61-70, normalised form):
+    (x + 1) / 2 * 255 in fp32, clipped to [0, 255], truncated - bit-exact against numpy (the library is built with
+    -ffp-contract=off).  A 4-D [B, C, H, W] tensor comes back as [B, H, W, C] (activations are NHWC in memory: no transpose), any
+    other shape as it is.  One launch of fsv_cast_half dir 2: what a video encoder takes, a quarter of the fp32 frame's bytes."""
+    if x.dtype != torch.float32:
+        raise ValueError("image_u8 converts fp32 tensors (got %s)" % x.dtype)
+    x = to_nhwc(x.detach()) if x.dim() == 4 else x.detach().contiguous()
+    if x.data_ptr() % 16:                    # (the kernel reads float4 vectors)
+        x = x.clone()
+    shape = (x.shape[0], x.shape[2], x.shape[3], x.shape[1]) if x.dim() == 4 else tuple(x.shape)
+    y = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    lib.check_device(x)
+    lib.call("fsv_cast_half", lib.ptr(x), lib.ptr(y), x.numel(), 2, lib.stream_ptr())
+    return y
+
+
 # ------------------------------------------------------------------------------------------------ spectral norm
 class SpectralState:
     """sigma bookkeeping for one weight: persistent u / v buffers live in the owning module."""
@@ -367,9 +384,20 @@ class _ConvFn(torch.autograd.Function):
         cache = getattr(weight, '_fsv_cache', None) if not per_sample else None
         entry = cache.lookup(weight, tuple(w4.shape), geom, cpad, up=bool(up and fold)) if cache is not None else None
         ctx.entry = entry
+        # frozen weights (infer.InferenceSession, no optimiser-owned cache): the layout of the un-cached path below - 1 / sigma
+        # baked into the re-arrangement - built ONCE by the session and kept until it refreezes; only for passes without a graph
+        frozen = getattr(weight, '_fsv_frozen', None) if (cache is None and not _keeps_graph(ctx)) else None
+        frozen = frozen.layout(weight, w4, geom, cpad, half, inv) if frozen is not None else None
+        w4_sub, inv_sub, up_cached = w4, inv, (entry.up_fwd if entry is not None else None)
         if entry is not None:
             wt, ldw = entry.fwd
             wscale = inv
+        elif frozen is not None:
+            wt, ldw = frozen.fwd
+            wscale = None if frozen.baked else inv
+            up_cached = frozen.up_fwd
+            if frozen.w4s is not None:        # a folded BatchNorm: the column factors (1 / sigma among them) are in the weights
+                w4_sub, inv_sub = frozen.w4s, None
         else:
             if cpad:
                 w4 = torch.nn.functional.pad(w4, (0, 0, 0, 0, 0, cpad))
@@ -401,7 +429,7 @@ class _ConvFn(torch.autograd.Function):
         # statistics instead; in-box A/B of round 6: profiles/r06_notes.md)
         if (y is None and fold and _up_subpixel_wanted(x.shape[0], x.shape[2], x.shape[3], cin, cout, geom, per_sample, res) and
                 (not st_wanted or _os.environ.get('FSV_UP_SUBPIXEL_STATS', '1') == '1')):
-            y = _up_subpixel_forward(x, w4, cout, b, act, scale, inv, cached=entry.up_fwd if entry is not None else None)
+            y = _up_subpixel_forward(x, w4_sub, cout, b, act, scale, inv_sub, cached=up_cached, keep=frozen)
         if y is None:
             y = conv_forward(x, wt, ldw, cout, geom, bias=b, res=res.detach() if res is not None else None, act=act,
                              scale=scale, per_sample=per_sample, wscale=wscale, stats=st, up=fold)
@@ -625,13 +653,13 @@ def _tap_sums(w4, rows):
     return torch.mm(w4.reshape(cout * cin, 9), k).view(cout, cin, 4, 4)
 
 
-def _up_subpixel_forward(x, w4, cout, bias, act, scale, wscale, cached=None):
+def _up_subpixel_forward(x, w4, cout, bias, act, scale, wscale, cached=None, keep=None):
     """y = act((conv3x3(nearest_x2(x), W) * wscale + bias) * scale) without the up-sampled tensor AND without its redundant
     products: output pixel 2s + r (r in {0,1} per axis) sees x[s - 1], x[s] (r = 0: weights W0, W1 + W2) resp. x[s], x[s + 1]
     (r = 1: W0 + W1, W2) - per parity class (ry, rx) a 2x2-tap convolution over x whose outputs are placed at stride 2
     (generator.py:489-493, 559-563: nn.Upsample(2) -> conv3x3).  The summed weights carry one fp32 rounding each against the
     reference's sum of the separate products.  x: NHWC fp32 at source resolution; w4: OIHW (un-normalised under spectral norm:
-    1 / sigma rides in wscale)."""
+    1 / sigma rides in wscale).  keep: a frozen-weight entry (infer.py) that takes the re-arrangement built here as its `up_fwd`."""
     n, cin, h, w = x.shape
     y = empty_nhwc(n, cout, 2 * h, 2 * w, x)
     # ONE re-arrangement for the four classes: 16 taps in class-major order, class c = K rows [c * 4 cin, (c + 1) * 4 cin)
@@ -646,6 +674,8 @@ def _up_subpixel_forward(x, w4, cout, bias, act, scale, wscale, cached=None):
         kws = [2 * rx + ix for ry, rx in cls for _ in (0, 1) for ix in (0, 1)]
         if one:
             wall, _, ldw = prep_weight(v, 0, Geom(3, 3, 1, 1), khs, kws, None)
+            if keep is not None and keep.can_grow():
+                keep.up_fwd = (wall, ldw)
     for c, (ry, rx) in enumerate(cls):
         ty = [ry - 1 + iy for iy in (0, 1) for _ in (0, 1)]                 # r = 0: x[s - 1], x[s]; r = 1: x[s], x[s + 1]
         tx = [rx - 1 + ix for _ in (0, 1) for ix in (0, 1)]
@@ -993,6 +1023,15 @@ def bn_backward(dy, y, x, mean, rstd, w, g, p, c, act, fixed_stats, affine, worl
     return dx, dw, db
 
 
+def _eval_stats(run_mean, run_var, eps):
+    """(mean, rstd) of an eval-mode BatchNorm from its running buffers; a frozen-weight session (infer.py) leaves the pair - the same
+    two operations, done once - on the buffer, valid while neither buffer is written again"""
+    kept = getattr(run_mean, '_fsv_frozen_stats', None)
+    if kept is not None and kept[0] == (run_mean._version, run_var._version, run_var.data_ptr(), float(eps)):
+        return kept[1]
+    return run_mean.detach().clone(), torch.rsqrt(run_var.detach() + eps)
+
+
 class _NormActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, run_mean, run_var, instance, eps, momentum, act, training):
@@ -1006,8 +1045,7 @@ class _NormActFn(torch.autograd.Function):
             mean, rstd = got if got is not None else norm_stats(
                 x, g, p, c, eps, None if instance else run_mean, None if instance else run_var, momentum, instance=instance)
         else:
-            mean = run_mean.detach().clone()
-            rstd = torch.rsqrt(run_var.detach() + eps)
+            mean, rstd = _eval_stats(run_mean, run_var, eps)
         y = torch.empty_like(x)
         wd = weight.detach().contiguous() if weight is not None else None
         bd = bias.detach().contiguous() if bias is not None else None
@@ -1233,6 +1271,17 @@ def _spade_launch(a):
                      _ll(a['wstr'] + [0]), _ll(a['bstr'] + [0]), n, hw, c, ldw, a.get('sbs', 0), a['act'], w, up, lib.stream_ptr())
 
 
+def _spade_plain_operand(w, g1):
+    """(K-major operand, Kpad) of one gamma / beta weight on the general SPADE path (channel counts the fast path declines): re-arranged
+    per call, or kept by a frozen-weight session (infer.py) like a convolution's layout"""
+    fz = getattr(w, '_fsv_frozen', None) if (getattr(w, '_fsv_cache', None) is None and not getattr(_outer_grad, 'on', True)) else None
+    e = fz.layout(w, w.detach(), g1, 0, False, None) if fz is not None else None
+    if e is not None:
+        return e.fwd[0], e.fwd[0].shape[-2]
+    t, kpad, _ = prep_weight(w.detach(), 0, g1)
+    return t, kpad
+
+
 class _SpadeFn(torch.autograd.Function):
     """h = act(spade(x; maps, weights)).  Argument list: x, run_mean, run_var, then per map (map, wg, wb, bg, bb).
 
@@ -1276,8 +1325,7 @@ class _SpadeFn(torch.autograd.Function):
             mean, rstd = got if got is not None else norm_stats(x, 1, n * xs_h * xs_w, c, eps, run_mean, run_var, momentum,
                                                                 rep=4 if up else 1)
         else:
-            mean = run_mean.detach().clone()
-            rstd = torch.rsqrt(run_var.detach() + eps)
+            mean, rstd = _eval_stats(run_mean, run_var, eps)
         g1 = Geom(1, 1, 1, 0)
         for k in range(nmaps):
             if tuple(maps[k].shape[2:]) != (h, w):
@@ -1329,10 +1377,16 @@ class _SpadeFn(torch.autograd.Function):
                 # generator-mode pass and its backward (LayoutCache.epoch: bumped by the refresh that ends every optimiser step;
                 # `_version` catches load_state_dict / copy_).  Round 6: 22 of the 46 preparation launches per step.
                 owner = getattr(wgs[k], '_fsv_cache', None) if (not per_sample and _os.environ.get('FSV_SPADE_PREP_CACHE', '1') == '1') else None
-                if owner is not None:
-                    key = (owner.epoch, wgs[k]._version, wbs[k]._version, bgs[k]._version, bbs[k]._version, wg.data_ptr(),
-                           wb.data_ptr(), bg.data_ptr(), bb.data_ptr(), c, ch, bool(ctx.f16))
-                    hit = getattr(wgs[k], '_fsv_spade_prep', None)
+                # frozen weights (infer.InferenceSession: fixed weights without an optimiser, and the generated weights kept for the
+                # sequence): the operands live in the SESSION, keyed by the tensors themselves, and are rewritten in place when it
+                # refills its buffers - nothing global that a later pass could find stale
+                fz = getattr(wgs[k], '_fsv_frozen', None) if (owner is None and not getattr(_outer_grad, 'on', True)) else None
+                same = (wg.data_ptr() == wgs[k].data_ptr() and wb.data_ptr() == wbs[k].data_ptr() and
+                        bg.data_ptr() == bgs[k].data_ptr() and bb.data_ptr() == bbs[k].data_ptr())
+                if owner is not None or fz is not None:
+                    key = (owner.epoch if owner is not None else -1, wgs[k]._version, wbs[k]._version, bgs[k]._version,
+                           bbs[k]._version, wg.data_ptr(), wb.data_ptr(), bg.data_ptr(), bb.data_ptr(), c, ch, bool(ctx.f16))
+                    hit = getattr(wgs[k], '_fsv_spade_prep', None) if owner is not None else fz.spade_get(wgs[k], key)
                     if hit is not None and hit[0] == key:
                         wcat_x, wcat_d, bcat = hit[1]
                         prepped += [wcat_x, wcat_d, bcat]
@@ -1340,9 +1394,9 @@ class _SpadeFn(torch.autograd.Function):
                             wg_p.append(wcat_x.data_ptr()); wb_p.append(wcat_x.data_ptr() + 2 * c * kt)
                         else:
                             wg_p.append(wcat_x.data_ptr()); wb_p.append(wcat_x.data_ptr() + 4 * c)
-                        wstr.append(0)
+                        wstr.append(2 * c * kt if per_sample else 0)            # (per-sample hits: a session's generated weights)
                         bg_p.append(bcat.data_ptr()); bb_p.append(bcat.data_ptr() + 4 * c)
-                        bstr.append(0)
+                        bstr.append(2 * c if per_sample else 0)
                         continue
                 # + 64 floats of slack: the beta half is addressed as (wcat_t + C) with the same row stride, so a channel
                 # tile that overhangs C (C not a multiple of the 32 / 64-wide tile) reads past the last row's end; those
@@ -1353,15 +1407,20 @@ class _SpadeFn(torch.autograd.Function):
                 wcat_d = torch.empty((nb, kd, ld), dtype=torch.float32, device=x.device) if need_d else None
                 bcat = torch.empty((nb, 2 * c), dtype=torch.float32, device=x.device)
                 lib.check_device(wg, wb, bg, bb)
-                lib.call("fsv_spade_prep", lib.ptr(wg), lib.ptr(wb), lib.ptr(bg), lib.ptr(bb),
-                         wg.stride(0) if per_sample else 0, wb.stride(0) if per_sample else 0,
-                         bg.stride(0) if per_sample else 0, bb.stride(0) if per_sample else 0,
-                         lib.ptr(wcat_t), lib.ptr(wcat_d), lib.ptr(bcat), nb, c, ch, lib.stream_ptr())
+                wcat_h = torch.empty((nb, 2 * c, kt), dtype=torch.float16, device=x.device) if ctx.f16 else None
+
+                def issue(wg=wg, wb=wb, bg=bg, bb=bb, per_sample=per_sample, wcat_t=wcat_t, wcat_d=wcat_d, bcat=bcat, nb=nb, ch=ch,
+                          wcat_h=wcat_h):
+                    lib.call("fsv_spade_prep", lib.ptr(wg), lib.ptr(wb), lib.ptr(bg), lib.ptr(bb),
+                             wg.stride(0) if per_sample else 0, wb.stride(0) if per_sample else 0,
+                             bg.stride(0) if per_sample else 0, bb.stride(0) if per_sample else 0,
+                             lib.ptr(wcat_t), lib.ptr(wcat_d), lib.ptr(bcat), nb, c, ch, lib.stream_ptr())
+                    if wcat_h is not None:
+                        # N-major half operand [nb][gamma rows (C) | beta rows (C)][Kh]
+                        lib.call("fsv_spade_prep_h", lib.ptr(wg), lib.ptr(wb), wg.stride(0) if per_sample else 0,
+                                 wb.stride(0) if per_sample else 0, lib.ptr(wcat_h), nb, c, ch, lib.stream_ptr())
+                issue()
                 if ctx.f16:
-                    # N-major half operand [nb][gamma rows (C) | beta rows (C)][Kh]
-                    wcat_h = torch.empty((nb, 2 * c, kt), dtype=torch.float16, device=x.device)
-                    lib.call("fsv_spade_prep_h", lib.ptr(wg), lib.ptr(wb), wg.stride(0) if per_sample else 0,
-                             wb.stride(0) if per_sample else 0, lib.ptr(wcat_h), nb, c, ch, lib.stream_ptr())
                     prepped += [wcat_h, wcat_d if need_d else flat_t[:0], bcat]
                     wg_p.append(wcat_h.data_ptr()); wb_p.append(wcat_h.data_ptr() + 2 * c * kt)
                     wstr.append(2 * c * kt if per_sample else 0)
@@ -1371,6 +1430,10 @@ class _SpadeFn(torch.autograd.Function):
                     wstr.append(kt * 2 * c if per_sample else 0)
                 if owner is not None:
                     wgs[k]._fsv_spade_prep = (key, tuple(prepped[-3:]))
+                elif fz is not None and same:
+                    # (`issue` writes the same operand tensors again from the same weight tensors: the session calls it after it
+                    # refilled generated weights in place)
+                    fz.spade_put((wgs[k], wbs[k], bgs[k], bbs[k]), key, tuple(prepped[-3:]), issue)
                 bg_p.append(bcat.data_ptr()); bb_p.append(bcat.data_ptr() + 4 * c)
                 bstr.append(2 * c if per_sample else 0)
             site = dict(x=x, mean=mean, rstd=rstd, h=hout, maps=maps, wg=wg_p, wb=wb_p, bg=bg_p, bb=bb_p, chs=chs, wstr=wstr,
@@ -1396,8 +1459,8 @@ class _SpadeFn(torch.autograd.Function):
         ldw = (c + 31) // 32 * 32
         for k in range(nmaps):
             per_sample = wgs[k].dim() == 5
-            tg, kpad, _ = prep_weight(wgs[k].detach(), 0, g1)
-            tb, _, _ = prep_weight(wbs[k].detach(), 0, g1)
+            tg, kpad = _spade_plain_operand(wgs[k], g1)
+            tb, _ = _spade_plain_operand(wbs[k], g1)
             wg_t.append(tg); wb_t.append(tb)
             bg_c.append(bgs[k].detach().contiguous()); bb_c.append(bbs[k].detach().contiguous())
             wbs_stride.append(kpad * ldw if per_sample else 0)

@@ -170,7 +170,8 @@ int fsv_hconv_prep_weight(const long long* jobs, const int* tmap, int nblocks, f
 /* the same for ONE layout with the geometry in the arguments (no device table: legal inside a graph capture) */
 int fsv_hconv_prep_weight_one(const float* src, void* dst, int Kpad32, int ldw, int nrows, int Kpad64, int nbatch,
                               fsv_stream_t stream);
-/* dense element conversion, dir 0: fp32 -> half (round to nearest even), 1: half -> fp32 */
+/* dense element conversion, dir 0: fp32 -> half (round to nearest even), 1: half -> fp32, 2: fp32 image in [-1, 1] -> uint8
+ * (y = n bytes): (x + 1) / 2 * 255 in fp32, clipped to [0, 255], truncated - a generated NHWC frame as a video encoder takes it */
 int fsv_cast_half(const void* x, void* y, long long n, int dir, fsv_stream_t stream);
 
 /* ---- narrow-operand GEMMs (csrc/conv_np.hip): the reference's `--amp` arithmetic (options/base_options.py:127,
@@ -204,10 +205,13 @@ int fsv_amp_update(float* scaler, fsv_stream_t stream);
 
 /* OIHW <-> K-major re-arrangement with an optional device scalar multiplier (the spectral-norm 1/sigma).
  * mode 0: wt[j*Cin+ci][co] = s*w[co][ci][kh_j][kw_j]; mode 1 (data gradient): wt[j*Cout+co][ci] = ...;
- * mode 2: inverse of mode 0 (gradients back to OIHW); mode 3: mode 2 accumulating into w. */
+ * mode 2: inverse of mode 0 (gradients back to OIHW); mode 3: mode 2 accumulating into w.
+ * col_scale (nullable, mode 0 without scale_ptr only; FSV_ERR_BAD_ARG otherwise): Cout per-output-channel factors shared by
+ * every sample of a batch, wt[j*Cin+ci][co] = w[co][ci][kh_j][kw_j] * col_scale[co] - a frozen eval-mode BatchNorm (and
+ * 1/sigma) folded into the layout. */
 int fsv_prep_weight(const float* w, float* wt, const float* scale_ptr, int mode, int nbatch,
                     int Cout, int Cin, int KH, int KW, int ntaps, const int* kh, const int* kw,
-                    int Kpad, int ldw, long long w_bstride, long long wt_bstride, fsv_stream_t stream);
+                    int Kpad, int ldw, long long w_bstride, long long wt_bstride, const float* col_scale, fsv_stream_t stream);
 
 /* every parameter weight of an optimiser re-arranged in one launch (un-scaled; used once per optimiser step).  dims[l] =
  * {Cout, Cin_pad, Cin_real, KH, KW, ntaps, Kpad, ldw, mode}; the layouts of one weight are consecutive in the tables and share
