@@ -810,6 +810,29 @@ __global__ __launch_bounds__(256) void fsv_cast_f2u8_kernel(const float* x, unsi
   for (long long e = (n4 << 2) + i; e < n; e += stride) y[e] = (unsigned char)fsv_u8_of(x[e]);
 }
 
+// uint8 image -> fp32 in [-1, 1] with the dataset's arithmetic (data/base_dataset.py get_transform: ToTensor, then Normalize(0.5,
+// 0.5)): v / 255 as a correctly rounded fp32 division, then (t - 0.5) / 0.5, every step rounded on its own (-ffp-contract=off) -
+// what torch computes for (x.float().div(255) - 0.5) / 0.5.  Four bytes enter as one 32-bit load and leave as one float4.
+__device__ __forceinline__ float fsv_f_of_u8(unsigned b) {
+#ifdef FSV_EMU
+  const float t = (float)b / 255.0f;
+#else
+  const float t = __fdiv_rn((float)b, 255.0f);
+#endif
+  return (t - 0.5f) / 0.5f;
+}
+__global__ __launch_bounds__(256) void fsv_cast_u82f_kernel(const unsigned char* x, float* y, long long n) {
+  const long long n4 = n >> 2;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long q = i; q < n4; q += stride) {
+    const unsigned v = reinterpret_cast<const unsigned*>(x)[q];
+    reinterpret_cast<float4*>(y)[q] = make_float4(fsv_f_of_u8(v & 255u), fsv_f_of_u8((v >> 8) & 255u), fsv_f_of_u8((v >> 16) & 255u),
+                                                  fsv_f_of_u8(v >> 24));
+  }
+  for (long long e = (n4 << 2) + i; e < n; e += stride) y[e] = fsv_f_of_u8(x[e]);
+}
+
 // =============================================== host side ===================================================
 static inline void fsv_h_pack_taps(const int* ty, const int* tx, int n, unsigned long long& lo, unsigned long long& hi) {
   lo = 0; hi = 0;
@@ -1120,16 +1143,20 @@ int fsv_hconv_prep_weight_one(const float* src, void* dst, int Kpad32, int ldw, 
   return fsv_check_launch();
 }
 
-// dense element conversion: dir 0 = fp32 -> half, 1 = half -> fp32, 2 = fp32 image in [-1, 1] -> uint8 (y = n bytes)
+// dense element conversion: dir 0 = fp32 -> half, 1 = half -> fp32, 2 = fp32 image in [-1, 1] -> uint8 (y = n bytes),
+// 3 = uint8 image (x = n bytes) -> fp32 in [-1, 1]
 int fsv_cast_half(const void* x, void* y, long long n, int dir, hipStream_t stream) {
-  if (!x || !y || n < 0 || dir < 0 || dir > 2) return FSV_ERR_BAD_ARG;
+  if (!x || !y || n < 0 || dir < 0 || dir > 3) return FSV_ERR_BAD_ARG;
+  // dir 3 reads the bytes as 32-bit words and stores float4 vectors
+  if (dir == 3 && ((((uintptr_t)x) & 3) != 0 || (((uintptr_t)y) & 15) != 0)) return FSV_ERR_BAD_ARG;
   if (n == 0) return FSV_OK;
   long long g = (n / 4 + 255) / 256;
   if (g > 8192) g = 8192;
   if (g < 1) g = 1;
   if (dir == 0) FSV_LAUNCH(fsv_cast_f2h_kernel, dim3((unsigned)g), dim3(256), stream, (const float*)x, (fsv_h16*)y, n);
   else if (dir == 1) FSV_LAUNCH(fsv_cast_h2f_kernel, dim3((unsigned)g), dim3(256), stream, (const fsv_h16*)x, (float*)y, n);
-  else FSV_LAUNCH(fsv_cast_f2u8_kernel, dim3((unsigned)g), dim3(256), stream, (const float*)x, (unsigned char*)y, n);
+  else if (dir == 2) FSV_LAUNCH(fsv_cast_f2u8_kernel, dim3((unsigned)g), dim3(256), stream, (const float*)x, (unsigned char*)y, n);
+  else FSV_LAUNCH(fsv_cast_u82f_kernel, dim3((unsigned)g), dim3(256), stream, (const unsigned char*)x, (float*)y, n);
   return fsv_check_launch();
 }
 

@@ -98,6 +98,39 @@ __global__ __launch_bounds__(256) void fsv_softmax_rows_fwd_kernel(const float* 
   }
 }
 
+// the same softmax, which also leaves gsum[row][g] = sum of y[row][j] over the g-th contiguous slice of L = C / groups channels (the
+// attention mass each of the n_shot references receives at a query position: generator.py:310,366 reduce the attention tensor twice
+// more for it).  Maximum, sum and normalisation are the code above, statement for statement, so y has the same bits; the store loop
+// walks the row slice by slice - a lane takes the elements j = lane (mod 64) of the slice, adds the values it stores in ascending j,
+// the wave folds the 64 partial sums in the butterfly order of the reductions above: fp32, a fixed order, no atomics.
+__global__ __launch_bounds__(256) void fsv_softmax_rows_gsum_kernel(const float* x, float* y, long long rows, int C, int groups,
+                                                                    float* gsum) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const bool ok = row < rows;
+  const float* xr = x + (ok ? row : 0) * C;
+  float m = -3.0e38f;
+  for (int j = lane; j < C; j += 64) m = fmaxf(m, xr[j]);
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  float s = 0.f;
+  for (int j = lane; j < C; j += 64) s += expf(xr[j] - m);
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  const float inv = 1.f / s;
+  float* yr = y + (ok ? row : 0) * C;
+  const int L = C / groups;
+  for (int g = 0; g < groups; ++g) {
+    const int lo = g * L, hi = lo + L;
+    float acc = 0.f;
+    for (int j = lo + ((lane - lo) & 63); j < hi; j += 64) {
+      const float v = expf(xr[j] - m) * inv;
+      if (ok) yr[j] = v;
+      acc += v;
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (ok && lane == 0) gsum[row * groups + g] = acc;
+  }
+}
+
 // dx = y * (dy - sum_j dy_j y_j)
 __global__ __launch_bounds__(256) void fsv_softmax_rows_bwd_kernel(const float* dy, const float* y, float* dx, long long rows, int C) {
   const int lane = threadIdx.x & 63;
@@ -208,9 +241,13 @@ int fsv_act_bwd(const float* dy, const float* y, float* dx, long long total, int
   return fsv_check_launch();
 }
 
-int fsv_softmax_rows_fwd(const float* x, float* y, long long rows, int C, hipStream_t stream) {
+// gsum != null: also gsum[rows][groups], the sums of y over the `groups` contiguous slices of C / groups channels (groups is not read
+// when gsum is null)
+int fsv_softmax_rows_fwd(const float* x, float* y, long long rows, int C, int groups, float* gsum, hipStream_t stream) {
   if (!x || !y || rows < 1 || C < 1) return FSV_ERR_BAD_ARG;
-  FSV_LAUNCH(fsv_softmax_rows_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, x, y, rows, C);
+  if (gsum && (groups < 1 || C % groups != 0)) return FSV_ERR_BAD_ARG;
+  if (gsum) FSV_LAUNCH(fsv_softmax_rows_gsum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, x, y, rows, C, groups, gsum);
+  else FSV_LAUNCH(fsv_softmax_rows_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, x, y, rows, C);
   return fsv_check_launch();
 }
 

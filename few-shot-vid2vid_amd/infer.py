@@ -6,7 +6,7 @@ optimiser, hence no layout_cache.LayoutCache), sigma of every spectral layer, th
 reference encoder's down path, the (mean, rstd) pair of every eval-mode BatchNorm.  An `InferenceSession` takes them once and keeps
 them until it is told that the weights changed:
 
-    sess = InferenceSession(model, opt, fold_norms=False, frames_u8=False, warmup=1)
+    sess = InferenceSession(model, opt, fold_norms=False, frames_u8=False, warmup=1, keep_references=False, inputs_u8=False)
     out = sess(tgt_label, ref_labels, ref_images)     # one frame: the six tensors of model.inference() (+ out.image_u8)
     sess.reset()                                      # between sequences (new references allowed)
     sess.refreeze()                                   # after anything changed the parameters or buffers
@@ -27,7 +27,26 @@ What is frozen and where it lives (everything belongs to the session: `close()` 
 Once per sequence (n_shot == 1): frame 0 runs `model.inference()` eagerly - with `--finetune` on the live weights, the session
 refreezes behind it - and leaves in static buffers the generated embed_w / norm_w / conv_w and the deepest reference feature x;
 `reset()` + a new frame 0 rewrites the same buffers in place (and the operands prepared from them), so a captured graph stays valid
-across sequences.  With n_shot > 1 reference encoding and attention depend on the frame and stay in the per-frame work.
+across sequences.  With n_shot > 1 reference encoding and attention depend on the frame and stay in the per-frame work - unless
+
+keep_references=True (n_shot > 1; a no-op with one reference): the reference side of the sequence is READ AT FRAME 0 AND KEPT.  In
+eval() every layer of the reference encoders is per sample (BatchNorm takes its running buffers, InstanceNorm is per sample
+anyway), so a reference's features up to the attention level and its keys depend on neither the frame nor the other inputs.  While
+frame 0 runs - model.inference() itself, eager and unchanged - the session collects the two kinds of operand the attention reads
+from the reference side, the key encoding of the reference labels (`kmat`) and the outputs of ref_img_down_{A-1} / ref_label_down_{A-1}
+(`xmat`; A = n_downsample_A), in the arrangement the GEMMs read, into static buffers of its own (`KeptReferences`); their K-major
+layouts are frozen like those of any other constant weight.  A steady frame then runs the query encoder, the energy GEMM, the
+softmax, the weighted sums and everything behind them (encoder levels A .. n-1, up path, pooled products, MLP bank, weight
+generation: they depend on the current label) on the same values, hence with the same bits; the mass per reference (atn_vis,
+ref_idx) comes out of the softmax launch (ops.softmax_channels groups) instead of two more reductions of the attention tensor, so
+atn_vis differs from the eager path's by the order of one fp32 sum.  THE DIFFERENCE TO model.inference(): that one re-reads
+ref_labels / ref_images on every frame; a session that keeps them ignores what is passed for them on frames t >= 1 (which is why
+the flag is opt-in).  reset() + a new frame 0 of equal shapes refills the buffers in place: the graph survives.  refreeze() drops
+them with the graph, and the next call is a frame 0.
+
+inputs_u8=True: the three inputs arrive as uint8 with the channel last ([B, 1, H, W, C] / [B, N, H, W, C]), as a video pipeline
+delivers them, and are converted on the device into the session's static inputs (ops.image_from_u8: the dataset's ToTensor +
+Normalize(0.5, 0.5), bit-exact).  Class-index label maps (label_nc != 0) are not covered: the flag raises for them.
 
 Replay (frames t >= 1): the conventions of graph_step.GraphedIteration - static input buffers, outputs as static tensors, the first
 `warmup` steady frames eager (they build what is built lazily), then ONE captured graph; a failed capture is recorded in
@@ -172,6 +191,49 @@ def count_graph_nodes(graph):
     return dict(kinds)
 
 
+class KeptReferences:
+    """the reference side of one sequence, owned by an InferenceSession (keep_references): netG._kept_refs.  `collect` takes what
+    frame 0's attention_module hands it; `keep` copies that into the static buffers kmat [b, n*hw, c, 1, 1] and xmats = [image
+    encoder's, label encoder's (not under 'concat')] [b, c, n*hw, 1, 1] - the per-sample 1x1 "weights" of the two attention GEMMs -
+    allocating them or, for equal shapes, rewriting them in place (-> True: the old buffers, and a graph captured over them,
+    stay valid)."""
+
+    def __init__(self):
+        self.ready, self.kmat, self.xmats = False, None, []
+        self._got = None
+
+    def begin(self):
+        self.ready, self._got = False, {}
+
+    def collect(self, name, t):
+        if self._got is not None:
+            self._got[name] = t                     # (the last pass wins: --finetune runs adaptation passes before the frame's own)
+
+    def abort(self):
+        self._got = None
+
+    def keep(self, frozen):
+        got, self._got = self._got, None
+        if not got or 'kmat' not in got or 'xmat0' not in got:
+            raise RuntimeError("keep_references: frame 0 did not pass through the attention module")
+        new = [got['kmat']] + [got[k] for k in ('xmat0', 'xmat1') if k in got]
+        old = ([self.kmat] + self.xmats) if self.kmat is not None else []
+        same = len(old) == len(new) and all(a.shape == b.shape and a.device == b.device for a, b in zip(old, new))
+        if same:
+            for dst, src in zip(old, new):
+                dst.copy_(src)
+        else:
+            old = [t.detach().clone(memory_format=torch.contiguous_format) for t in new]
+            self.kmat, self.xmats = old[0], old[1:]
+        for t in old:
+            t._fsv_frozen = frozen
+        self.ready = True
+        return same
+
+    def drop(self):
+        self.ready, self.kmat, self.xmats, self._got = False, None, [], None
+
+
 class FrameOutputs(tuple):
     """(fake, raw, warped, flow, mask, atn_score) of Vid2VidModel.inference; `image_u8` ([B, H, W, 3] uint8) with frames_u8"""
     image_u8 = None
@@ -196,7 +258,7 @@ def _flat_tensors(obj, out=None):
 
 
 class InferenceSession:
-    def __init__(self, model, opt, fold_norms=False, frames_u8=False, warmup=1):
+    def __init__(self, model, opt, fold_norms=False, frames_u8=False, warmup=1, keep_references=False, inputs_u8=False):
         model = getattr(model, 'module', model)
         if model.training:
             raise RuntimeError("InferenceSession freezes the weights: put the model in eval() first (it is in train() mode)")
@@ -205,6 +267,14 @@ class InferenceSession:
                                "are kept for the sequence)")
         self.model, self.opt = model, opt
         self.fold_norms, self.frames_u8 = bool(fold_norms), bool(frames_u8)
+        self.inputs_u8 = bool(inputs_u8)
+        if self.inputs_u8 and getattr(opt, 'label_nc', 0) != 0:
+            raise ValueError("inputs_u8 converts image-like labels (pose, face sketches); class-index label maps (label_nc = %d) "
+                             "are not covered" % opt.label_nc)
+        netG = model.netG
+        # keep_references: only where there is an attention module to feed (n_shot > 1); with one reference the flag is a no-op
+        self.keep_references = bool(keep_references) and netG.n_shot > 1 and 1 <= netG.n_downsample_A <= netG.n_downsample_G
+        self._kept = KeptReferences() if self.keep_references else None
         self.warmup = max(int(warmup), 1)      # at least one eager steady frame: it builds what the capture may not
         self.capture_failures = []             # (signature, first line of the error) of every capture that fell back to eager frames
         self.n_captures = 0
@@ -214,6 +284,8 @@ class InferenceSession:
             raise RuntimeError("InferenceSession needs a GPU (hipGraph capture)")
         self.frozen = None
         self._tagged = []
+        if self._kept is not None:
+            netG._kept_refs = self._kept
         self._drop_graph()
         self._drop_buffers()
         self._sig = None
@@ -245,6 +317,9 @@ class InferenceSession:
             self.folded_sites = self._fold() if self.fold_norms else []
         for t in _flat_tensors(self._static_w):
             t._fsv_frozen = fz
+        if self._kept is not None and self._kept.kmat is not None:
+            for t in [self._kept.kmat] + self._kept.xmats:
+                t._fsv_frozen = fz
 
     def _fold_candidates(self, net):
         for name, m in net.named_modules():
@@ -282,6 +357,10 @@ class InferenceSession:
         for t in _flat_tensors(self._static_w):
             if getattr(t, '_fsv_frozen', None) is not None:
                 del t._fsv_frozen
+        if self._kept is not None and self._kept.kmat is not None:
+            for t in [self._kept.kmat] + self._kept.xmats:
+                if getattr(t, '_fsv_frozen', None) is not None:
+                    del t._fsv_frozen
         for m in self._spectral:
             m._sig_frozen = None
         for rm in self._bn_buffers:
@@ -295,10 +374,14 @@ class InferenceSession:
     def refreeze(self):
         """after anything changed the parameters or buffers (load_state_dict, a finetune): take every constant again.  The captured
         graph read the old ones and is dropped; within a running sequence the reference feature is recomputed per frame, as the
-        eager path does, until the next frame 0 keeps it again."""
+        eager path does, until the next frame 0 keeps it again.  With keep_references the kept reference side was encoded by the
+        old weights: it is dropped, and the next call is a frame 0."""
         self._detach()
         self._drop_graph()
         self.model.netG._frozen_x = None
+        if self._kept is not None:
+            self._kept.drop()
+            self.reset()
         self._attach()
 
     def close(self):
@@ -306,6 +389,10 @@ class InferenceSession:
         self._detach()
         self._drop_graph()
         self.model.netG._frozen_x = None
+        if self._kept is not None:
+            self._kept.drop()
+            if self.model.netG.__dict__.get('_kept_refs') is self._kept:
+                del self.model.netG._kept_refs
         self._drop_buffers()
         if getattr(self.model, '_infer_session', None) is self:
             self.model._infer_session = None
@@ -323,7 +410,9 @@ class InferenceSession:
         self._graph, self._graph_has_x, self._out, self._steady, self._eager_only = None, False, None, 0, False
 
     def _drop_buffers(self):
-        self._in = self._ring = self._static_w = self._static_x = None
+        self._in = self._ring = self._static_w = self._static_x = self._ref_in = None
+        if getattr(self, '_kept', None) is not None:
+            self._kept.drop()
 
     keep_graph = False       # tools/infer_session.py sets it before the capture: the hipGraph stays queryable (graph_nodes)
 
@@ -356,14 +445,31 @@ class InferenceSession:
         if finetune:
             self._detach()                       # the adaptation steps train on the live weights
             self._drop_graph()
+        kept = self._kept
+        if self.inputs_u8:
+            tgt_label = ops.image_from_u8(tgt_label)
+        if kept is not None or self.inputs_u8:
+            # the references of the sequence in static buffers of the session's own: the steady frames read them there
+            ref_labels, ref_images = self._hold_references(ref_labels, ref_images)
+        if kept is not None:
+            kept.begin()                         # (not ready: frame 0 is the eager path, which hands its operands to `kept`)
         try:
             out = model.inference(tgt_label, ref_labels, ref_images)
+        except BaseException:
+            if kept is not None:
+                kept.abort()
+            raise
         finally:
             if finetune:
                 self._attach()
         with torch.no_grad():
             if netG.n_shot == 1 and ref_labels.shape[1] == 1:
                 self._keep_sequence()
+            if kept is not None:
+                if kept.keep(self.frozen):
+                    self.frozen.refill()         # rewritten in place: so are the layouts prepared from them
+                elif self._graph is not None:
+                    self._drop_graph()
             if self._ring is None:
                 self._ring = [p.detach().clone() for p in model.prevs]
             else:
@@ -372,6 +478,21 @@ class InferenceSession:
             model.prevs = self._ring
         self.t = 0
         return self._wrap(out, out[0])
+
+    def _hold_references(self, ref_labels, ref_images):
+        """frame 0 with keep_references / inputs_u8: the sequence's references (converted from uint8 where they arrive so) into
+        static buffers - allocated for new shapes, rewritten in place otherwise"""
+        refs = (ref_labels, ref_images)
+        if self._ref_in is None:
+            # (_in is None here as well: the two are dropped together, _drop_buffers)
+            self._ref_in = [ops.image_from_u8(t) if self.inputs_u8 else t.detach().clone() for t in refs]
+        else:
+            for dst, src in zip(self._ref_in, refs):
+                if self.inputs_u8:
+                    ops.image_from_u8(src, out=dst)
+                else:
+                    dst.copy_(src)
+        return self._ref_in
 
     def _keep_sequence(self):
         """generated weights and the deepest reference feature of this sequence into the session's static buffers"""
@@ -451,11 +572,23 @@ class InferenceSession:
         ins = (tgt_label, ref_labels, ref_images)
         if self._signature(ins) != self._sig:
             raise RuntimeError("the frame's tensors changed shape, dtype or device inside a sequence; call reset() first")
+        held = self._kept is not None and self._ref_in is not None      # the references were read at frame 0
         if self._in is None:
-            self._in = [t.detach().clone() for t in ins]
+            tgt = ops.image_from_u8(tgt_label) if self.inputs_u8 else tgt_label.detach().clone()
+            if held:
+                self._in = [tgt] + list(self._ref_in)
+            elif self.inputs_u8:
+                self._in = [tgt] + list(self._ref_in)
+                for dst, src in zip(self._in[1:], ins[1:]):
+                    ops.image_from_u8(src, out=dst)
+            else:
+                self._in = [tgt] + [t.detach().clone() for t in ins[1:]]
         else:
-            for dst, src in zip(self._in, ins):
-                dst.copy_(src, non_blocking=True)
+            for dst, src in zip(self._in, ins[:1] if held else ins):
+                if self.inputs_u8:
+                    ops.image_from_u8(src, out=dst)
+                else:
+                    dst.copy_(src, non_blocking=True)
         self._steady += 1
         if self._emulated or self._eager_only or self._steady <= self.warmup:
             if not self._emulated and self._steady == 1:

@@ -830,7 +830,15 @@ class Vid2VidModel(nn.Module):
     _infer_session = None
 
     def inference_session(self, **kw):
-        """an infer.InferenceSession over this model (fold_norms=False, frames_u8=False, warmup=1); the caller drives it"""
+        """an infer.InferenceSession over this model (fold_norms=False, frames_u8=False, warmup=1, keep_references=False,
+        inputs_u8=False); the caller drives it.
+        keep_references=True (n_shot > 1; a no-op with one reference): the reference side of a sequence - the reference encoders up
+        to the attention level and the attention keys - is read at frame 0 and kept until reset() / refreeze().  Unlike
+        inference(), which re-reads ref_labels / ref_images on every frame, such a session ignores the references passed on
+        frames t >= 1.  The hook sits on netG (like the kept feature of one reference): while such a session is attached and
+        inside a sequence, do not call inference() on this model directly - it would take the kept reference side too and
+        silently ignore the references it is given; close() the session first.
+        inputs_u8=True: the three inputs are uint8 with the channel last and are converted on the device (ops.image_from_u8)."""
         from . import infer
         return infer.InferenceSession(self, self.opt, **kw)
 

@@ -776,34 +776,66 @@ class FewShotGenerator(nn.Module):
         n = self.n_shot
         b = bn // n
         hw = h * w
+        # an infer.InferenceSession with keep_references collects the two GEMM operands of the reference side while frame 0 runs
+        # (the tensors this pass builds anyway: nothing more is launched here)
+        sink = getattr(self, '_kept_refs', None) if not torch.is_grad_enabled() else None
+        which = 0 if attention is None else 1
         if attention is None:
             key = self.attention_encode(label_ref, 'atn_key')            # [b*n, c, h, w]
             query = self.attention_encode(label, 'atn_query')            # [b, c, h, w]
             kmat = key.reshape(b, n, c, hw).permute(0, 1, 3, 2).reshape(b, n * hw, c, 1, 1)
             energy_t = ops.batch_conv(query, kmat, allow_half=False)                        # [b, n*hw, h, w]
             attention = ops.softmax_channels(energy_t)
+            if sink is not None:
+                sink.collect('kmat', kmat)
         xmat = x.reshape(b, n, c, hw).permute(0, 2, 1, 3).reshape(b, c, n * hw, 1, 1)
+        if sink is not None:
+            sink.collect('xmat%d' % which, xmat)
         out = ops.batch_conv(attention, xmat, allow_half=False)                             # [b, c, h, w]
         atn_vis = attention.reshape(b, n, hw, h, w).sum(2)[-1:, 0:1]
         return out, attention, atn_vis
+
+    def attention_module_kept(self, kept, label):
+        """attention_module on the operands an infer.InferenceSession kept from frame 0 (`keep_references`): kept.kmat is the key
+        encoding of the reference labels and kept.xmats the reference features that enter the attention (image encoder, then label
+        encoder), each in the arrangement its GEMM reads.  Per frame: the query encoder, the energy GEMM, the softmax and the
+        weighted sums - the same launches on the same values as attention_module, so the same bits.  The mass each reference
+        receives comes out of the softmax launch (ops.softmax_channels groups): the attention tensor is not read again.
+        Returns ([attended image feature, attended label feature or None], atn_vis, ref_idx)."""
+        query = self.attention_encode(label, 'atn_query')
+        energy_t = ops.batch_conv(query, kept.kmat, allow_half=False)
+        attention, mass = ops.softmax_channels(energy_t, groups=self.n_shot)           # mass [b, h, w, n]
+        outs = [ops.batch_conv(attention, xm, allow_half=False) for xm in kept.xmats]
+        atn_vis = mass.permute(0, 3, 1, 2)[-1:, 0:1]
+        ref_idx = torch.argmax(mass.sum((1, 2)), dim=1)
+        return outs + [None] * (2 - len(outs)), atn_vis, ref_idx
 
     def reference_encoding(self, img_ref, label_ref, encode=True, label=None):
         n = self.n_downsample_G
         # (the two encoders as parallel branches of the captured graph: +2 ... 3 ms in round 2, re-measured in round 6 on the final
         # kernels: 42.32 / 42.65 -> 43.50 / 43.51 ms per step - profiles/r06_step_ab_schedule.txt; not kept)
         concat = self.concat_label_ref
-        if concat:               # generator.py:342-345: one encoder on [image | label]
+        # the reference side a session kept at frame 0 (infer.InferenceSession keep_references): in eval() every layer of the
+        # encoders is per sample, so levels 0 .. A - 1 and the key encoder give the same tensors on every frame of the sequence
+        kept = getattr(self, '_kept_refs', None)
+        if kept is not None and not (kept.ready and self.n_shot > 1 and not torch.is_grad_enabled() and not self.training):
+            kept = None
+        first = 0
+        atn = atn_vis = ref_idx = None
+        if kept is not None:
+            (x, xl), atn_vis, ref_idx = self.attention_module_kept(kept, label)
+            first = self.n_downsample_A
+        elif concat:             # generator.py:342-345: one encoder on [image | label]
             x = self.ref_img_first(ops.cat_channels([img_ref, label_ref]))
             xl = None
         else:
             x = self.ref_img_first(img_ref)
             xl = self.ref_label_first(label_ref)
-        atn = atn_vis = ref_idx = None
-        for i in range(n):
+        for i in range(first, n):
             x = getattr(self, 'ref_img_down_%d' % i)(x)
             if not concat:
                 xl = getattr(self, 'ref_label_down_%d' % i)(xl)
-            if self.n_shot > 1 and i == self.n_downsample_A - 1:          # generator.py:359-366
+            if kept is None and self.n_shot > 1 and i == self.n_downsample_A - 1:          # generator.py:359-366
                 x, atn, atn_vis = self.attention_module(x, label, label_ref)
                 if not concat:
                     xl, _, _ = self.attention_module(xl, None, None, atn)

@@ -110,7 +110,7 @@ class _SoftmaxChFn(torch.autograd.Function):
         n, c, h, w = x.shape
         y = torch.empty_like(x)
         lib.check_device(x)
-        lib.call("fsv_softmax_rows_fwd", lib.ptr(x), lib.ptr(y), n * h * w, c, lib.stream_ptr())
+        lib.call("fsv_softmax_rows_fwd", lib.ptr(x), lib.ptr(y), n * h * w, c, 0, None, lib.stream_ptr())
         ctx.save_for_backward(y)
         return y
 
@@ -124,9 +124,23 @@ class _SoftmaxChFn(torch.autograd.Function):
         return dx
 
 
-def softmax_channels(x):
-    """nn.Softmax(dim=1) on an NCHW tensor (generator.py:384): a row softmax in channels-last memory."""
-    return _SoftmaxChFn.apply(x)
+def softmax_channels(x, groups=0):
+    """nn.Softmax(dim=1) on an NCHW tensor (generator.py:384): a row softmax in channels-last memory.
+    groups > 0 (forward only): returns (y, mass), mass[b, h, w, g] = the sum of y over the g-th contiguous slice of C / groups
+    channels, taken by the same launch from the values it stores (fp32, fixed order); y has the bits of the groups=0 call."""
+    if not groups:
+        return _SoftmaxChFn.apply(x)
+    if x.requires_grad and torch.is_grad_enabled():
+        raise ValueError("softmax_channels(groups > 0) is forward-only (the tensor requires grad)")
+    x = to_nhwc(x.detach())
+    n, c, h, w = x.shape
+    if groups < 1 or c % groups:
+        raise ValueError("softmax_channels: %d groups do not divide %d channels" % (groups, c))
+    y = torch.empty_like(x)
+    mass = torch.empty((n, h, w, groups), dtype=torch.float32, device=x.device)
+    lib.check_device(x)
+    lib.call("fsv_softmax_rows_fwd", lib.ptr(x), lib.ptr(y), n * h * w, c, int(groups), lib.ptr(mass), lib.stream_ptr())
+    return y, mass
 
 
 # ------------------------------------------------------------------------------------------------ column sums
@@ -157,6 +171,34 @@ def image_u8(x):
     lib.check_device(x)
     lib.call("fsv_cast_half", lib.ptr(x), lib.ptr(y), x.numel(), 2, lib.stream_ptr())
     return y
+
+
+def image_from_u8(x, out=None):
+    """uint8 image [..., H, W, C] -> the fp32 tensor the model takes, logical [..., C, H, W] on the same channel-last memory (no
+    transpose), with the dataset's arithmetic (ToTensor, Normalize(0.5, 0.5)): (v / 255 - 0.5) / 0.5, every step rounded on its
+    own - bit-exact against torch ON THE HOST, the dataset's path.  (torch on a device tensor divides by a scalar through its fp32
+    reciprocal: a caller who normalises uint8 frames with torch on the device gets other last bits for some byte values.)  One
+    launch of fsv_cast_half dir 3.  `out`: a tensor this function returned before for the same shape (16-byte aligned), rewritten
+    in place."""
+    if x.dtype != torch.uint8 or x.dim() < 3:
+        raise ValueError("image_from_u8 converts [..., H, W, C] uint8 tensors (got %s, %d-D)" % (x.dtype, x.dim()))
+    if lib.is_emu() == x.is_cuda:
+        raise lib.FsvError("image_from_u8: the tensor is on the wrong device for the loaded kernel library")
+    x = x.detach().contiguous()
+    if x.data_ptr() % 4:                     # (the kernel reads four bytes as one word)
+        x = x.clone()
+    nd = x.dim()
+    perm = tuple(range(nd - 3)) + (nd - 1, nd - 3, nd - 2)
+    if out is None:
+        y = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+    else:
+        y = out.permute(tuple(range(nd - 3)) + (nd - 2, nd - 1, nd - 3))
+        if out.dtype != torch.float32 or tuple(y.shape) != tuple(x.shape) or not y.is_contiguous() or out.device != x.device:
+            raise ValueError("image_from_u8: `out` is not a tensor of this function for the shape %s" % (tuple(x.shape),))
+        if y.data_ptr() % 16:                # (the kernel stores float4 vectors)
+            raise ValueError("image_from_u8: `out` is not 16-byte aligned")
+    lib.call("fsv_cast_half", lib.ptr(x), lib.ptr(y), x.numel(), 3, lib.stream_ptr())
+    return out if out is not None else y.permute(perm)
 
 
 # ------------------------------------------------------------------------------------------------ spectral norm

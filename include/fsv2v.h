@@ -171,7 +171,10 @@ int fsv_hconv_prep_weight(const long long* jobs, const int* tmap, int nblocks, f
 int fsv_hconv_prep_weight_one(const float* src, void* dst, int Kpad32, int ldw, int nrows, int Kpad64, int nbatch,
                               fsv_stream_t stream);
 /* dense element conversion, dir 0: fp32 -> half (round to nearest even), 1: half -> fp32, 2: fp32 image in [-1, 1] -> uint8
- * (y = n bytes): (x + 1) / 2 * 255 in fp32, clipped to [0, 255], truncated - a generated NHWC frame as a video encoder takes it */
+ * (y = n bytes): (x + 1) / 2 * 255 in fp32, clipped to [0, 255], truncated - a generated NHWC frame as a video encoder takes it;
+ * 3: uint8 (x = n bytes) -> fp32 in [-1, 1], the dataset's ToTensor + Normalize(0.5, 0.5): v / 255, then (t - 0.5) / 0.5, each step
+ * rounded to fp32 on its own - a decoded frame as the model takes it; dir 3 needs x 4-byte and y 16-byte aligned (the bytes
+ * are read as 32-bit words, the result is stored as float4): FSV_ERR_BAD_ARG otherwise */
 int fsv_cast_half(const void* x, void* y, long long n, int dir, fsv_stream_t stream);
 
 /* ---- narrow-operand GEMMs (csrc/conv_np.hip): the reference's `--amp` arithmetic (options/base_options.py:127,
@@ -501,8 +504,11 @@ int fsv_adaptive_avgpool_bwd(const float* dy, float* dx, int N, int H, int W, in
  * OW <= 40) */
 int fsv_pool_rows_fwd(const float* x, float* rows, int N, int H, int W, int C, int OH, int OW, fsv_stream_t stream);
 int fsv_pool_rows_bwd(const float* drows, float* dx, int N, int H, int W, int C, int OH, int OW, fsv_stream_t stream);
-/* softmax over the contiguous channel dimension of [rows][C] (nn.Softmax(dim=1) at generator.py:384) */
-int fsv_softmax_rows_fwd(const float* x, float* y, long long rows, int C, fsv_stream_t stream);
+/* softmax over the contiguous channel dimension of [rows][C] (nn.Softmax(dim=1) at generator.py:384).  gsum != NULL: the launch
+ * also writes gsum[rows][groups], gsum[row][g] = the sum of y[row][j] over the g-th contiguous slice of C / groups channels (the
+ * attention mass per reference, generator.py:310,366), accumulated in fp32 in a fixed order, no atomics; y has the same bits with
+ * and without gsum.  groups < 1 or C % groups != 0 with a non-null gsum: FSV_ERR_BAD_ARG (groups is not read when gsum is NULL) */
+int fsv_softmax_rows_fwd(const float* x, float* y, long long rows, int C, int groups, float* gsum, fsv_stream_t stream);
 int fsv_softmax_rows_bwd(const float* dy, const float* y, float* dx, long long rows, int C, fsv_stream_t stream);
 /* state = {t, 1-beta1^t, 1-beta2^t, lr} on the device; gscale pre-multiplies the gradient (1/world_size) */
 int fsv_adam_step(float* param, const float* grad, float* m, float* v, float* state, long long n, float beta1,
