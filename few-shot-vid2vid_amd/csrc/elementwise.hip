@@ -241,11 +241,19 @@ int fsv_act_bwd(const float* dy, const float* y, float* dx, long long total, int
   return fsv_check_launch();
 }
 
+// Per-launch bound of the row softmax (forward and backward): one wave per row, four rows per 256-thread workgroup, and a launch
+// holds fewer than 2^32 work-items per grid dimension - so at most FSV_SOFTMAX_MAX_ROWS rows; more is FSV_ERR_UNSUPPORTED, nothing
+// launched (the cast of the workgroup count to 32 bits used to wrap silently).  Inside the bound nothing is 32-bit: a row's base is
+// (long long)row * C elements on a 64-bit pointer, so rows * C may exceed 2^31 elements (the attention bands of n_shot > 1:
+// 16384 rows of 32768 ... 65536 channels).  y == x is allowed: every lane stores exactly the elements it alone read.
+#define FSV_SOFTMAX_MAX_ROWS (4ll * 0xffffffll)
+
 // gsum != null: also gsum[rows][groups], the sums of y over the `groups` contiguous slices of C / groups channels (groups is not read
 // when gsum is null)
 int fsv_softmax_rows_fwd(const float* x, float* y, long long rows, int C, int groups, float* gsum, hipStream_t stream) {
   if (!x || !y || rows < 1 || C < 1) return FSV_ERR_BAD_ARG;
   if (gsum && (groups < 1 || C % groups != 0)) return FSV_ERR_BAD_ARG;
+  if (rows > FSV_SOFTMAX_MAX_ROWS) return FSV_ERR_UNSUPPORTED;
   if (gsum) FSV_LAUNCH(fsv_softmax_rows_gsum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, x, y, rows, C, groups, gsum);
   else FSV_LAUNCH(fsv_softmax_rows_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, x, y, rows, C);
   return fsv_check_launch();
@@ -253,6 +261,7 @@ int fsv_softmax_rows_fwd(const float* x, float* y, long long rows, int C, int gr
 
 int fsv_softmax_rows_bwd(const float* dy, const float* y, float* dx, long long rows, int C, hipStream_t stream) {
   if (!dy || !y || !dx || rows < 1 || C < 1) return FSV_ERR_BAD_ARG;
+  if (rows > FSV_SOFTMAX_MAX_ROWS) return FSV_ERR_UNSUPPORTED;
   FSV_LAUNCH(fsv_softmax_rows_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, dy, y, dx, rows, C);
   return fsv_check_launch();
 }

@@ -201,6 +201,15 @@ class KeptReferences:
     def __init__(self):
         self.ready, self.kmat, self.xmats = False, None, []
         self._got = None
+        self.band = None
+
+    def band_buffer(self, numel, device):
+        """the one energy / attention band of a banded attention (networks._attention_bands_nograd): the session's, like the other
+        static buffers - allocated by the eager warm-up frame, the same memory on every replay (the plan, and with it the size, is
+        fixed by the shapes the graph was captured for; other shapes drop the graph and this buffer together)"""
+        if self.band is None or self.band.numel() < numel or self.band.device != device:
+            self.band = torch.empty(numel, dtype=torch.float32, device=device)
+        return self.band
 
     def begin(self):
         self.ready, self._got = False, {}
@@ -231,7 +240,7 @@ class KeptReferences:
         return same
 
     def drop(self):
-        self.ready, self.kmat, self.xmats, self._got = False, None, [], None
+        self.ready, self.kmat, self.xmats, self._got, self.band = False, None, [], None, None
 
 
 class FrameOutputs(tuple):

@@ -10,6 +10,7 @@ BN+LeakyReLU, SPADE denorm+modulate+LeakyReLU).
 """
 import contextlib
 import math
+import os
 import weakref
 
 import torch
@@ -17,7 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, streams
-from .conv import ACT_LRELU, ACT_NONE, ACT_SIGMOID, ACT_TANH
+from .conv import ACT_LRELU, ACT_NONE, ACT_SIGMOID, ACT_TANH, empty_nhwc, to_nhwc
 
 
 # ------------------------------------------------------------------------------------------------ parameter holders
@@ -523,6 +524,113 @@ def pick_ref(refs, ref_idx):
     return refs[torch.arange(refs.shape[0], device=refs.device), ref_idx.long()]
 
 
+# ------------------------------------------------------------------------------------------------ attention in query bands
+# The attention of n_shot > 1 (generator.py:298-316) materialises energy / attention [b, n*hw, h, w] in fp32; one gather-GEMM launch
+# reads at most ATTN_LAUNCH_MAX_BYTES of input, all samples of the launch together (include/fsv2v.h, csrc/conv_igemm.h
+# FSV_BUF_MAX_BYTES).  The softmax is over the n*hw key positions of each query pixel, so query pixels are independent: the three
+# launches (energy GEMM, softmax, weighted sums) run per BAND of query positions - a range of whole samples, or a range of rows of
+# the h x w query grid of one sample; either is one dense piece of channels-last memory - against the same key / reference operands.
+ATTN_LAUNCH_MAX_BYTES = 1 << 31
+
+
+def attention_band_plan(b, n, hw, h, w):
+    """-> None: one launch covers the attention and FSV_ATTN_BAND_MB is unset (the unbanded code runs, launch for launch), else the
+    bands [(s0, s1, r0, r1)]: samples s0 .. s1 - 1, rows r0 .. r1 - 1.  The largest bands whose energy / attention slice stays at or
+    under min(ATTN_LAUNCH_MAX_BYTES, FSV_ATTN_BAND_MB * 2^20): whole samples while one sample fits (the per-sample launches count the
+    bytes of all their samples), rows of one sample otherwise - the last band of a sample (of the batch) takes the remainder.
+    FSV_ATTN_BAND_MB (a number, fractions allowed; read per call): for tests and A/B runs."""
+    cap = ATTN_LAUNCH_MAX_BYTES
+    forced = os.environ.get('FSV_ATTN_BAND_MB', '')
+    if forced:
+        mb = float(forced)
+        if not mb > 0:
+            raise ValueError("FSV_ATTN_BAND_MB=%r: a positive number of MiB expected" % forced)
+        cap = min(cap, int(mb * (1 << 20)))
+    row_bytes = n * hw * w * 4
+    sample_bytes = row_bytes * h
+    if not forced and b * sample_bytes <= cap:
+        return None
+    if sample_bytes <= cap:
+        per = min(b, cap // sample_bytes)
+        return [(s, min(b, s + per), 0, h) for s in range(0, b, per)]
+    rows = cap // row_bytes
+    if rows < 1:
+        raise ValueError("attention: one row of %d query positions against %d x %d key positions is %d bytes, over the %d of one band"
+                         % (w, n, hw, row_bytes, cap))
+    return [(s, s + 1, r, min(h, r + rows)) for s in range(b) for r in range(0, h, rows)]
+
+
+class AttentionBands:
+    """what attention_module hands out as `atn` in banded mode instead of the attention tensor: the per-reference masses
+    mass[b, h, w, n] (the sum of the attention over each reference's hw key positions: atn_vis and ref_idx), the bands' attention
+    tensors where they live on anyway (with autograd: saved for backward), the second feature map's result when it was taken from the
+    same band loop, and the small operands a later call needs to run the bands again (no_grad, second map not announced)."""
+
+    def __init__(self, plan, b, n, hw, h, w):
+        self.plan, self.b, self.n, self.hw, self.h, self.w = plan, b, n, hw, h, w
+        self.mass = None
+        self.bands = None            # [attention of band i] (autograd mode)
+        self.second = None           # (the tensor it was computed for, its attended feature)
+        self.query = self.kmat = None
+
+    @property
+    def shape(self):
+        return (self.b, self.n * self.hw, self.h, self.w)
+
+    def atn_vis(self):
+        return self.mass.permute(0, 3, 1, 2)[-1:, 0:1]
+
+    def ref_idx(self):
+        return torch.argmax(self.mass.sum((1, 2)), dim=1)
+
+
+def _xmat(x, b, n, hw):
+    """reference features [b*n, c, h, w] as the per-sample 1x1 weights [b, c, n*hw, 1, 1] of the weighted-sum GEMM"""
+    c = x.shape[1]
+    return x.reshape(b, n, c, hw).permute(0, 2, 1, 3).reshape(b, c, n * hw, 1, 1)
+
+
+def _attention_bands_nograd(query, kmat, xmats, atn, band_buffer=None):
+    """the band loop without autograd: ONE band of energy lives at a time - the softmax runs in place - in a buffer reused across
+    the bands; the masses come out of the softmax launch.  -> [attended feature per xmat], atn.mass filled"""
+    b, n, hw, h, w = atn.b, atn.n, atn.hw, atn.h, atn.w
+    query = to_nhwc(query.detach())
+    kop = ops.batch_conv_operand(kmat)
+    xops = [ops.batch_conv_operand(xm) for xm in xmats]
+    outs = [empty_nhwc(b, xm.shape[1], h, w, query) for xm in xmats]
+    mass = torch.empty((b, h, w, n), dtype=torch.float32, device=query.device)
+    need = max((s1 - s0) * (r1 - r0) for s0, s1, r0, r1 in atn.plan) * w * n * hw
+    buf = band_buffer(need, query.device) if band_buffer is not None else torch.empty(need, dtype=torch.float32, device=query.device)
+    for s0, s1, r0, r1 in atn.plan:
+        s, rows = s1 - s0, r1 - r0
+        e = buf[:s * rows * w * n * hw].view(s, rows, w, n * hw).permute(0, 3, 1, 2)
+        ops.batch_conv_band(query[s0:s1, :, r0:r1], kop, s0, out=e)
+        ops.softmax_channels(e, groups=n, out=e, mass=mass[s0:s1, r0:r1])
+        for o, xop in zip(outs, xops):
+            ops.batch_conv_band(e, xop, s0, out=o[s0:s1, :, r0:r1])
+    atn.mass = mass
+    return outs
+
+
+def _attention_bands_grad(query, kmat, xmats, atn):
+    """the band loop with autograd: every band is the differentiable chain of the unbanded code on a slice of the query (its
+    attention is saved for backward, so the bands stay alive: atn.bands); the masses are detached reductions of each band; the
+    outputs are assembled by ONE concatenation of [pixels, c] pieces - the bands are consecutive pieces of channels-last memory"""
+    b, n, hw, h, w = atn.b, atn.n, atn.hw, atn.h, atn.w
+    bands, pieces, masses = [], [[] for _ in xmats], []
+    for s0, s1, r0, r1 in atn.plan:
+        s, rows = s1 - s0, r1 - r0
+        a = ops.softmax_channels(ops.batch_conv(query[s0:s1, :, r0:r1], kmat[s0:s1], allow_half=False))
+        bands.append(a)
+        masses.append(a.detach().reshape(s, n, hw, rows * w).sum(2).permute(0, 2, 1).reshape(s * rows * w, n))
+        for p, xm in zip(pieces, xmats):
+            o = ops.batch_conv(a, xm[s0:s1], allow_half=False)
+            p.append(o.permute(0, 2, 3, 1).reshape(s * rows * w, o.shape[1]))
+    atn.bands = bands
+    atn.mass = torch.cat(masses, 0).view(b, h, w, n)
+    return [torch.cat(p, 0).view(b, h, w, -1).permute(0, 3, 1, 2) for p in pieces]
+
+
 class FewShotGenerator(nn.Module):
     """Reference generator.py:20-454 without the KLD branch; n_shot >= 1 (with more than one reference image the attention module
     of generator.py:291-316 merges the reference features).  use_label_ref 'mul' (two encoders, softmax-pooled channel products
@@ -780,6 +888,11 @@ class FewShotGenerator(nn.Module):
         # (the tensors this pass builds anyway: nothing more is launched here)
         sink = getattr(self, '_kept_refs', None) if not torch.is_grad_enabled() else None
         which = 0 if attention is None else 1
+        if isinstance(attention, AttentionBands):
+            return self._attention_second(x, attention, sink)
+        plan = attention_band_plan(b, n, hw, h, w) if attention is None else None
+        if plan is not None:
+            return self._attention_banded(x, label, label_ref, AttentionBands(plan, b, n, hw, h, w), sink)
         if attention is None:
             key = self.attention_encode(label_ref, 'atn_key')            # [b*n, c, h, w]
             query = self.attention_encode(label, 'atn_query')            # [b, c, h, w]
@@ -795,6 +908,51 @@ class FewShotGenerator(nn.Module):
         atn_vis = attention.reshape(b, n, hw, h, w).sum(2)[-1:, 0:1]
         return out, attention, atn_vis
 
+    def _attention_banded(self, x, label, label_ref, atn, sink):
+        """attention_module in query bands (attention_band_plan): the same three launches per band, on the same values, against
+        kmat / xmat operands prepared once.  A second feature map announced by reference_encoding (self._atn_second: the label
+        features under use_label_ref 'mul') is attended in the same loop, while the band exists; the later call
+        attention_module(xl, None, None, atn) then only picks its result up."""
+        b, n, hw = atn.b, atn.n, atn.hw
+        second = self.__dict__.pop('_atn_second', None)
+        key = self.attention_encode(label_ref, 'atn_key')            # [b*n, c, h, w]
+        query = self.attention_encode(label, 'atn_query')            # [b, c, h, w]
+        kmat = key.reshape(b, n, key.shape[1], hw).permute(0, 1, 3, 2).reshape(b, n * hw, key.shape[1], 1, 1)
+        xs = [x] + ([second] if second is not None else [])
+        xmats = [_xmat(t, b, n, hw) for t in xs]
+        if sink is not None:
+            sink.collect('kmat', kmat)
+            for i, xm in enumerate(xmats):
+                sink.collect('xmat%d' % i, xm)
+        if torch.is_grad_enabled():
+            outs = _attention_bands_grad(query, kmat, xmats, atn)
+        else:
+            outs = _attention_bands_nograd(query, kmat, xmats, atn)
+            atn.query, atn.kmat = query, kmat
+        if second is not None:
+            atn.second = (second, outs[1])
+        return outs[0], atn, atn.atn_vis()
+
+    def _attention_second(self, x, atn, sink):
+        """attention_module(x, None, None, atn) with the banded attention `atn`: the result taken in the first call's band loop, or
+        (a caller that did not announce the map) the bands once more"""
+        if atn.second is not None and atn.second[0] is x:
+            return atn.second[1], atn, atn.atn_vis()
+        xmat = _xmat(x, atn.b, atn.n, atn.hw)
+        if sink is not None:
+            sink.collect('xmat1', xmat)
+        if atn.bands is not None:
+            pieces = []
+            for (s0, s1, r0, r1), a in zip(atn.plan, atn.bands):
+                o = ops.batch_conv(a, xmat[s0:s1], allow_half=False)
+                pieces.append(o.permute(0, 2, 3, 1).reshape(-1, o.shape[1]))
+            out = torch.cat(pieces, 0).view(atn.b, atn.h, atn.w, -1).permute(0, 3, 1, 2)
+        elif atn.query is not None and not torch.is_grad_enabled():
+            out = _attention_bands_nograd(atn.query, atn.kmat, [xmat], atn)[0]
+        else:
+            raise RuntimeError("banded attention: the attention of this pass was not kept for a second feature map")
+        return out, atn, atn.atn_vis()
+
     def attention_module_kept(self, kept, label):
         """attention_module on the operands an infer.InferenceSession kept from frame 0 (`keep_references`): kept.kmat is the key
         encoding of the reference labels and kept.xmats the reference features that enter the attention (image encoder, then label
@@ -803,6 +961,13 @@ class FewShotGenerator(nn.Module):
         receives comes out of the softmax launch (ops.softmax_channels groups): the attention tensor is not read again.
         Returns ([attended image feature, attended label feature or None], atn_vis, ref_idx)."""
         query = self.attention_encode(label, 'atn_query')
+        b, nhw = kept.kmat.shape[:2]
+        h, w = query.shape[2:]
+        plan = attention_band_plan(b, self.n_shot, nhw // self.n_shot, h, w)
+        if plan is not None:             # in query bands, the band buffer the session's own (static under a captured graph)
+            atn = AttentionBands(plan, b, self.n_shot, nhw // self.n_shot, h, w)
+            outs = _attention_bands_nograd(query, kept.kmat, kept.xmats, atn, kept.band_buffer)
+            return outs + [None] * (2 - len(outs)), atn.atn_vis(), atn.ref_idx()
         energy_t = ops.batch_conv(query, kept.kmat, allow_half=False)
         attention, mass = ops.softmax_channels(energy_t, groups=self.n_shot)           # mass [b, h, w, n]
         outs = [ops.batch_conv(attention, xm, allow_half=False) for xm in kept.xmats]
@@ -836,10 +1001,18 @@ class FewShotGenerator(nn.Module):
             if not concat:
                 xl = getattr(self, 'ref_label_down_%d' % i)(xl)
             if kept is None and self.n_shot > 1 and i == self.n_downsample_A - 1:          # generator.py:359-366
-                x, atn, atn_vis = self.attention_module(x, label, label_ref)
+                if not concat:           # (banded attention: the label features are attended in the image features' band loop)
+                    self._atn_second = xl
+                try:
+                    x, atn, atn_vis = self.attention_module(x, label, label_ref)
+                finally:
+                    self.__dict__.pop('_atn_second', None)
                 if not concat:
                     xl, _, _ = self.attention_module(xl, None, None, atn)
-                ref_idx = torch.argmax(atn.reshape(label.shape[0], self.n_shot, -1).sum(2), dim=1)
+                if isinstance(atn, AttentionBands):
+                    ref_idx = atn.ref_idx()
+                else:
+                    ref_idx = torch.argmax(atn.reshape(label.shape[0], self.n_shot, -1).sum(2), dim=1)
         self._atn = (atn_vis, ref_idx)
         if not encode:           # generator.py:370: test-time frames after the first re-use the cached weights
             return x, None

@@ -124,11 +124,15 @@ class _SoftmaxChFn(torch.autograd.Function):
         return dx
 
 
-def softmax_channels(x, groups=0):
+def softmax_channels(x, groups=0, out=None, mass=None):
     """nn.Softmax(dim=1) on an NCHW tensor (generator.py:384): a row softmax in channels-last memory.
     groups > 0 (forward only): returns (y, mass), mass[b, h, w, g] = the sum of y over the g-th contiguous slice of C / groups
-    channels, taken by the same launch from the values it stores (fp32, fixed order); y has the bits of the groups=0 call."""
+    channels, taken by the same launch from the values it stores (fp32, fixed order); y has the bits of the groups=0 call.
+    out / mass (groups > 0): dense channels-last tensors to write instead of new ones; `out` may be x itself (in place: a lane stores
+    only the elements it alone read - the banded attention keeps ONE band in memory this way)."""
     if not groups:
+        if out is not None or mass is not None:
+            raise ValueError("softmax_channels: out / mass belong to the forward-only form (groups > 0)")
         return _SoftmaxChFn.apply(x)
     if x.requires_grad and torch.is_grad_enabled():
         raise ValueError("softmax_channels(groups > 0) is forward-only (the tensor requires grad)")
@@ -136,9 +140,17 @@ def softmax_channels(x, groups=0):
     n, c, h, w = x.shape
     if groups < 1 or c % groups:
         raise ValueError("softmax_channels: %d groups do not divide %d channels" % (groups, c))
-    y = torch.empty_like(x)
-    mass = torch.empty((n, h, w, groups), dtype=torch.float32, device=x.device)
-    lib.check_device(x)
+    if out is None:
+        y = torch.empty_like(x)
+    else:
+        y = out.detach()
+        if y.shape != x.shape or y.dtype != torch.float32 or not y.permute(0, 2, 3, 1).is_contiguous():
+            raise ValueError("softmax_channels: `out` must be a dense channels-last fp32 tensor of the input's shape")
+    if mass is None:
+        mass = torch.empty((n, h, w, groups), dtype=torch.float32, device=x.device)
+    elif tuple(mass.shape) != (n, h, w, groups) or mass.dtype != torch.float32 or not mass.is_contiguous():
+        raise ValueError("softmax_channels: `mass` must be a contiguous fp32 [n, h, w, groups] tensor")
+    lib.check_device(x, y, mass)
     lib.call("fsv_softmax_rows_fwd", lib.ptr(x), lib.ptr(y), n * h * w, c, int(groups), lib.ptr(mass), lib.stream_ptr())
     return y, mass
 
@@ -994,6 +1006,42 @@ def batch_conv(x, weight, bias=None, act=ACT_NONE, stride=1, allow_half=True, re
     # read them in place (sample stride), no copies here
     _note_grad_mode()
     return _ConvFn.apply(x, weight, bias, res, None, None, None, geom, act, 1.0, False, 0, allow_half)
+
+
+def batch_conv_operand(weight):
+    """The K-major GEMM operand of batch_conv(x, weight, allow_half=False) for generated 1x1 weights [B, Cout, Cin, 1, 1], laid out
+    ONCE for a caller that issues the product in several launches over bands of x (the attention of n_shot > 1 in query bands,
+    networks.FewShotGenerator): -> (wt [B, Kpad, ldw], ldw, Cout).  The same fsv_prep_weight call on the same values as _ConvFn's
+    un-cached path - or the layout an infer.InferenceSession already keeps for this tensor - so a band has the bits a call of
+    batch_conv on the band alone would have."""
+    w4 = weight.detach()
+    if w4.dim() != 5 or w4.shape[-1] != 1 or w4.shape[-2] != 1:
+        raise ValueError("batch_conv_operand: generated 1x1 weights [B, Cout, Cin, 1, 1] expected, got %s" % (tuple(w4.shape),))
+    geom = Geom(1, 1, 1, 0)
+    frozen = getattr(weight, '_fsv_frozen', None)
+    lay = frozen.layout(weight, w4, geom, 0, False, None) if frozen is not None else None
+    if lay is not None:
+        wt, ldw = lay.fwd
+    else:
+        wt, _, ldw = prep_weight(w4, 0, geom)
+    return wt, ldw, w4.shape[1]
+
+
+def batch_conv_band(x, operand, s0, out=None):
+    """batch_conv over a band: x [s, Cin, rows, w] holds rows of the samples s0 .. s0 + s - 1 of the batch `operand`
+    (batch_conv_operand) was generated for; forward only, exact fp32.  out: the dense channels-last tensor to write."""
+    wt, ldw, cout = operand
+    s = x.shape[0]
+    if x.requires_grad and torch.is_grad_enabled():
+        raise ValueError("batch_conv_band is forward-only (a band that needs a gradient is a batch_conv call)")
+    if s0 < 0 or s0 + s > wt.shape[0]:
+        raise ValueError("batch_conv_band: samples %d .. %d of %d" % (s0, s0 + s - 1, wt.shape[0]))
+    if out is not None and (tuple(out.shape) != (s, cout, x.shape[2], x.shape[3]) or out.dtype != torch.float32 or
+                            not out.permute(0, 2, 3, 1).is_contiguous()):
+        raise ValueError("batch_conv_band: `out` must be a dense channels-last fp32 [%d, %d, %d, %d] tensor"
+                         % (s, cout, x.shape[2], x.shape[3]))
+    geom = Geom(1, 1, 1, 0)
+    return gather_gemm(x.detach(), wt[s0:s0 + s], ldw, cout, x.shape[2], x.shape[3], geom.ty, geom.tx, 1, 1, per_sample=True, out=out)
 
 
 # ------------------------------------------------------------------------------------------------ normalisation

@@ -51,7 +51,11 @@ enum fsv_gan_mode { FSV_GAN_HINGE = 0 /* loss.py:69-79 */, FSV_GAN_LS = 1 /* :57
  * the caller, results are added (used for the four parity classes of a stride-2 data gradient).
  * force_tile / force_split: -1 / 0 = automatic; a tile id is a row of the tile-variant table (csrc/conv_igemm.hip FSV_CONV_TILES,
  * readable through fsv_conv_tile_info): FSV_ERR_BAD_ARG for any other id.
- * One activation tensor / weight matrix may hold at most 2 GiB (32-bit byte offsets): FSV_ERR_UNSUPPORTED beyond.  wscale: optional device scalar multiplying the accumulator before
+ * Per-launch bounds: the INPUT tensor of one launch - all N samples together, also with per_sample != 0, whose kernels form a
+ * sample's pixels as 32-bit byte offsets from the base of the batch - and one weight matrix may hold at most 2 GiB each:
+ * FSV_ERR_UNSUPPORTED beyond, nothing launched.  `out` (and res / the split-K copies) is addressed with 64-bit element offsets and
+ * has no bound of its own below 2^31 pixels per launch.  A caller with more (the attention of n_shot > 1, networks.py) issues
+ * the launch in bands of samples / rows, each inside these bounds.  wscale: optional device scalar multiplying the accumulator before
  * the bias (the spectral-norm 1/sigma when wt holds un-normalised weights). */
 /* split_ws / split_ws_floats (nullable; ordered split-K): when the call's plan splits K, split k stores its partial output into
  * the k-th copy inside split_ws (nsplit x N*outH*outW*Cout floats) and the copies are summed in ascending order: the same bits on
@@ -507,7 +511,10 @@ int fsv_pool_rows_bwd(const float* drows, float* dx, int N, int H, int W, int C,
 /* softmax over the contiguous channel dimension of [rows][C] (nn.Softmax(dim=1) at generator.py:384).  gsum != NULL: the launch
  * also writes gsum[rows][groups], gsum[row][g] = the sum of y[row][j] over the g-th contiguous slice of C / groups channels (the
  * attention mass per reference, generator.py:310,366), accumulated in fp32 in a fixed order, no atomics; y has the same bits with
- * and without gsum.  groups < 1 or C % groups != 0 with a non-null gsum: FSV_ERR_BAD_ARG (groups is not read when gsum is NULL) */
+ * and without gsum.  groups < 1 or C % groups != 0 with a non-null gsum: FSV_ERR_BAD_ARG (groups is not read when gsum is NULL).
+ * Per-launch bounds (forward and backward): rows <= 4 * (2^24 - 1) = 67108860 (four rows per 256-thread workgroup, fewer than 2^32
+ * work-items per launch): FSV_ERR_UNSUPPORTED beyond, nothing launched.  Rows are addressed as 64-bit element offsets, rows * C
+ * is not bounded by 2^31.  The forward pass may run in place (y == x). */
 int fsv_softmax_rows_fwd(const float* x, float* y, long long rows, int C, int groups, float* gsum, fsv_stream_t stream);
 int fsv_softmax_rows_bwd(const float* dy, const float* y, float* dx, long long rows, int C, fsv_stream_t stream);
 /* state = {t, 1-beta1^t, 1-beta2^t, lr} on the device; gscale pre-multiplies the gradient (1/world_size) */
