@@ -6,7 +6,8 @@ optimiser, hence no layout_cache.LayoutCache), sigma of every spectral layer, th
 reference encoder's down path, the (mean, rstd) pair of every eval-mode BatchNorm.  An `InferenceSession` takes them once and keeps
 them until it is told that the weights changed:
 
-    sess = InferenceSession(model, opt, fold_norms=False, frames_u8=False, warmup=1, keep_references=False, inputs_u8=False)
+    sess = InferenceSession(model, opt, fold_norms=False, frames_u8=False, warmup=1, keep_references=False, inputs_u8=False,
+                            fused_attention=False)
     out = sess(tgt_label, ref_labels, ref_images)     # one frame: the six tensors of model.inference() (+ out.image_u8)
     sess.reset()                                      # between sequences (new references allowed)
     sess.refreeze()                                   # after anything changed the parameters or buffers
@@ -43,6 +44,14 @@ atn_vis differs from the eager path's by the order of one fp32 sum.  THE DIFFERE
 ref_labels / ref_images on every frame; a session that keeps them ignores what is passed for them on frames t >= 1 (which is why
 the flag is opt-in).  reset() + a new frame 0 of equal shapes refills the buffers in place: the graph survives.  refreeze() drops
 them with the graph, and the next call is a frame 0.
+
+fused_attention=True (n_shot > 1): every frame of the session - frame 0, the eager warm-up and the captured steady frame - runs the
+attention as the one streaming launch of ops.attention_fused (csrc/attention.hip; a graph node like any other): no energy /
+attention tensor, no band loop, no band buffer.  With keep_references the session then keeps the key encoding and the reference
+features as the encoders wrote them (their own NHWC memory: `KeptReferences.key` / `.vals`), which is what that kernel reads, and
+no kmat / xmat arrangement with its K-major layouts.  Not bit-equal to the eager frames: the summation order of the softmax and of
+the weighted sums changes (a shape the kernel does not serve runs the launches above).  The mark sits on netG until close()
+(like the kept reference side): model.inference() or another session on the same model is fused too while this one is attached.
 
 inputs_u8=True: the three inputs arrive as uint8 with the channel last ([B, 1, H, W, C] / [B, N, H, W, C]), as a video pipeline
 delivers them, and are converted on the device into the session's static inputs (ops.image_from_u8: the dataset's ToTensor +
@@ -192,7 +201,10 @@ def count_graph_nodes(graph):
 
 
 class KeptReferences:
-    """the reference side of one sequence, owned by an InferenceSession (keep_references): netG._kept_refs.  `collect` takes what
+    """the reference side of one sequence, owned by an InferenceSession (keep_references): netG._kept_refs.  After a fused frame 0
+    (fused_attention) it is `key` [b n, c, h, w] and `vals` = [image encoder's, label encoder's (not under 'concat')] [b n, cv, h, w],
+    dense NHWC clones of the encoders' outputs - what ops.attention_fused reads - and kmat / xmats / band stay empty; no layout is
+    frozen for them.  Otherwise: `collect` takes what
     frame 0's attention_module hands it; `keep` copies that into the static buffers kmat [b, n*hw, c, 1, 1] and xmats = [image
     encoder's, label encoder's (not under 'concat')] [b, c, n*hw, 1, 1] - the per-sample 1x1 "weights" of the two attention GEMMs -
     allocating them or, for equal shapes, rewriting them in place (-> True: the old buffers, and a graph captured over them,
@@ -200,6 +212,7 @@ class KeptReferences:
 
     def __init__(self):
         self.ready, self.kmat, self.xmats = False, None, []
+        self.key, self.vals = None, []           # a fused frame 0 (ops.attention_fused): the encoders' outputs as they lie in memory
         self._got = None
         self.band = None
 
@@ -223,24 +236,34 @@ class KeptReferences:
 
     def keep(self, frozen):
         got, self._got = self._got, None
-        if not got or 'kmat' not in got or 'xmat0' not in got:
+        fused = bool(got) and 'key' in got and 'val0' in got
+        if not fused and (not got or 'kmat' not in got or 'xmat0' not in got):
             raise RuntimeError("keep_references: frame 0 did not pass through the attention module")
-        new = [got['kmat']] + [got[k] for k in ('xmat0', 'xmat1') if k in got]
-        old = ([self.kmat] + self.xmats) if self.kmat is not None else []
+        if fused:
+            new = [got['key']] + [got[k] for k in ('val0', 'val1') if k in got]
+            old = ([self.key] + self.vals) if self.key is not None else []
+        else:
+            new = [got['kmat']] + [got[k] for k in ('xmat0', 'xmat1') if k in got]
+            old = ([self.kmat] + self.xmats) if self.kmat is not None else []
         same = len(old) == len(new) and all(a.shape == b.shape and a.device == b.device for a, b in zip(old, new))
         if same:
             for dst, src in zip(old, new):
                 dst.copy_(src)
+        elif fused:
+            old = [ops.to_nhwc(t.detach()).clone() for t in new]           # (clone keeps the dense NHWC strides)
+            self.key, self.vals, self.kmat, self.xmats, self.band = old[0], old[1:], None, [], None
         else:
             old = [t.detach().clone(memory_format=torch.contiguous_format) for t in new]
-            self.kmat, self.xmats = old[0], old[1:]
-        for t in old:
-            t._fsv_frozen = frozen
+            self.kmat, self.xmats, self.key, self.vals = old[0], old[1:], None, []
+        if not fused:                            # (the fused kernel reads the kept tensors themselves: no layout to freeze)
+            for t in old:
+                t._fsv_frozen = frozen
         self.ready = True
         return same
 
     def drop(self):
         self.ready, self.kmat, self.xmats, self._got, self.band = False, None, [], None, None
+        self.key, self.vals = None, []
 
 
 class FrameOutputs(tuple):
@@ -267,7 +290,8 @@ def _flat_tensors(obj, out=None):
 
 
 class InferenceSession:
-    def __init__(self, model, opt, fold_norms=False, frames_u8=False, warmup=1, keep_references=False, inputs_u8=False):
+    def __init__(self, model, opt, fold_norms=False, frames_u8=False, warmup=1, keep_references=False, inputs_u8=False,
+                 fused_attention=False):
         model = getattr(model, 'module', model)
         if model.training:
             raise RuntimeError("InferenceSession freezes the weights: put the model in eval() first (it is in train() mode)")
@@ -295,6 +319,10 @@ class InferenceSession:
         self._tagged = []
         if self._kept is not None:
             netG._kept_refs = self._kept
+        # fused_attention: the mark networks.attention_fused_switch reads, on netG for as long as the session is attached
+        self.fused_attention = bool(fused_attention) and netG.n_shot > 1
+        if self.fused_attention:
+            netG._attn_fused = True
         self._drop_graph()
         self._drop_buffers()
         self._sig = None
@@ -402,6 +430,8 @@ class InferenceSession:
             self._kept.drop()
             if self.model.netG.__dict__.get('_kept_refs') is self._kept:
                 del self.model.netG._kept_refs
+        if self.fused_attention:
+            self.model.netG.__dict__.pop('_attn_fused', None)
         self._drop_buffers()
         if getattr(self.model, '_infer_session', None) is self:
             self.model._infer_session = None

@@ -831,7 +831,12 @@ class Vid2VidModel(nn.Module):
 
     def inference_session(self, **kw):
         """an infer.InferenceSession over this model (fold_norms=False, frames_u8=False, warmup=1, keep_references=False,
-        inputs_u8=False); the caller drives it.
+        inputs_u8=False, fused_attention=False); the caller drives it.
+        fused_attention=True (n_shot > 1): the session's frames run the attention as one streaming launch (ops.attention_fused) -
+        no [n hw, hw] tensor, no band loop; with keep_references the key / reference features are kept as the encoders wrote them.
+        Like the kept reference side, the mark sits on netG until close(): while such a session is attached, inference() on this
+        model and any other session on it take the streaming attention too - close() the session first (a session that is dropped
+        without close() leaves the mark behind).
         keep_references=True (n_shot > 1; a no-op with one reference): the reference side of a sequence - the reference encoders up
         to the attention level and the attention keys - is read at frame 0 and kept until reset() / refreeze().  Unlike
         inference(), which re-reads ref_labels / ref_images on every frame, such a session ignores the references passed on

@@ -584,6 +584,35 @@ class AttentionBands:
         return torch.argmax(self.mass.sum((1, 2)), dim=1)
 
 
+class AttentionFused(AttentionBands):
+    """the `atn` of the streaming attention (ops.attention_fused, FSV_ATTN_FUSED / an InferenceSession's fused_attention): no band
+    plan and no attention tensor at all - the masses of the one launch, the second feature map's result when it was announced, and
+    the query / key features a later call for an unannounced map walks again"""
+
+    def __init__(self, b, n, hw, h, w):
+        AttentionBands.__init__(self, None, b, n, hw, h, w)
+        self.key = None
+
+
+def attention_fused_switch(net=None):
+    """FSV_ATTN_FUSED (0 / 1, default 0; read per call), or a network an InferenceSession(fused_attention=True) marked: the attention
+    of n_shot > 1 as one streaming launch - where autograd is off and ops.attention_fused serves the shape; ignored otherwise"""
+    if torch.is_grad_enabled():
+        return False
+    if net is not None and net.__dict__.get('_attn_fused', False):
+        return True
+    v = os.environ.get('FSV_ATTN_FUSED', '')
+    if not v:
+        return False
+    try:
+        f = float(v)
+    except ValueError:
+        f = -1.0
+    if f not in (0.0, 1.0):
+        raise ValueError("FSV_ATTN_FUSED=%r: 0 or 1 expected" % v)
+    return f == 1.0
+
+
 def _xmat(x, b, n, hw):
     """reference features [b*n, c, h, w] as the per-sample 1x1 weights [b, c, n*hw, 1, 1] of the weighted-sum GEMM"""
     c = x.shape[1]
@@ -890,6 +919,10 @@ class FewShotGenerator(nn.Module):
         which = 0 if attention is None else 1
         if isinstance(attention, AttentionBands):
             return self._attention_second(x, attention, sink)
+        if attention is None and attention_fused_switch(self):
+            second = self.__dict__.get('_atn_second', None)
+            if ops.attention_fused_serves(b, n, hw, c, [c] + ([second.shape[1]] if second is not None else [])):
+                return self._attention_fused(x, label, label_ref, AttentionFused(b, n, hw, h, w), sink)
         plan = attention_band_plan(b, n, hw, h, w) if attention is None else None
         if plan is not None:
             return self._attention_banded(x, label, label_ref, AttentionBands(plan, b, n, hw, h, w), sink)
@@ -933,11 +966,35 @@ class FewShotGenerator(nn.Module):
             atn.second = (second, outs[1])
         return outs[0], atn, atn.atn_vis()
 
+    def _attention_fused(self, x, label, label_ref, atn, sink):
+        """attention_module as ONE streaming launch (ops.attention_fused) on the encoders' outputs as they lie in memory: no kmat /
+        xmat arrangement, no energy or attention tensor.  An announced second feature map (self._atn_second) rides in the same
+        launch."""
+        second = self.__dict__.pop('_atn_second', None)
+        key = self.attention_encode(label_ref, 'atn_key')            # [b*n, c, h, w]
+        query = self.attention_encode(label, 'atn_query')            # [b, c, h, w]
+        vals = [x] + ([second] if second is not None else [])
+        outs, atn.mass = ops.attention_fused(query, key, vals, atn.n)
+        atn.query, atn.key = query, key
+        if second is not None:
+            atn.second = (second, outs[1])
+        if sink is not None:
+            sink.collect('key', key)
+            for i, t in enumerate(vals):
+                sink.collect('val%d' % i, t)
+        return outs[0], atn, atn.atn_vis()
+
     def _attention_second(self, x, atn, sink):
         """attention_module(x, None, None, atn) with the banded attention `atn`: the result taken in the first call's band loop, or
         (a caller that did not announce the map) the bands once more"""
         if atn.second is not None and atn.second[0] is x:
             return atn.second[1], atn, atn.atn_vis()
+        if isinstance(atn, AttentionFused):        # not announced: a second launch over the same query / key features
+            if atn.query is None or torch.is_grad_enabled():
+                raise RuntimeError("fused attention: the attention of this pass was not kept for a second feature map")
+            if sink is not None:
+                sink.collect('val1', x)
+            return ops.attention_fused(atn.query, atn.key, [x], atn.n, want_mass=False)[0][0], atn, atn.atn_vis()
         xmat = _xmat(x, atn.b, atn.n, atn.hw)
         if sink is not None:
             sink.collect('xmat1', xmat)
@@ -961,6 +1018,9 @@ class FewShotGenerator(nn.Module):
         receives comes out of the softmax launch (ops.softmax_channels groups): the attention tensor is not read again.
         Returns ([attended image feature, attended label feature or None], atn_vis, ref_idx)."""
         query = self.attention_encode(label, 'atn_query')
+        if kept.key is not None:         # kept by a fused frame 0: the key / reference features in their own NHWC memory
+            outs, mass = ops.attention_fused(query, kept.key, kept.vals, self.n_shot)
+            return outs + [None] * (2 - len(outs)), mass.permute(0, 3, 1, 2)[-1:, 0:1], torch.argmax(mass.sum((1, 2)), dim=1)
         b, nhw = kept.kmat.shape[:2]
         h, w = query.shape[2:]
         plan = attention_band_plan(b, self.n_shot, nhw // self.n_shot, h, w)

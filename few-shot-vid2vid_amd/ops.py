@@ -1044,6 +1044,73 @@ def batch_conv_band(x, operand, s0, out=None):
     return gather_gemm(x.detach(), wt[s0:s0 + s], ldw, cout, x.shape[2], x.shape[3], geom.ty, geom.tx, 1, 1, per_sample=True, out=out)
 
 
+def _attention_fused_plan(b, n, p, c, cvs, want_mass, split):
+    """(nsplit, workspace floats) of fsv_attention_fused_fwd for this shape, or None when the kernel does not serve it"""
+    out = (ctypes.c_longlong * 2)()
+    rc = lib.call_status("fsv_attention_fused_plan", b, n, p, c, cvs[0], cvs[1] if len(cvs) > 1 else 0, 1 if want_mass else 0,
+                         int(split), out)
+    if rc == lib.ENUMS['FSV_ERR_UNSUPPORTED']:
+        return None
+    if rc != 0:
+        raise lib.FsvError("fsv_attention_fused_plan failed with fsv_status %d" % rc)
+    return int(out[0]), int(out[1])
+
+
+def attention_fused_serves(b, n, p, c, cvs):
+    """the same question from the sizes alone: b samples, n references, p = h w positions, c key / query channels, cvs the channel
+    counts of the one or two value maps"""
+    return 1 <= len(cvs) <= 2 and min(b, n, p, c) >= 1 and _attention_fused_plan(b, n, p, c, list(cvs), True, 0) is not None
+
+
+def attention_fused_supported(query, key, values, n):
+    """whether attention_fused serves these tensors (fp32, one or two value maps, every channel count a multiple of 4 up to 256):
+    a caller asks before it chooses the fused path, nothing is launched"""
+    ts = [query, key] + list(values)
+    if not 1 <= len(values) <= 2 or n < 1 or any(t.dim() != 4 or t.dtype != torch.float32 for t in ts):
+        return False
+    b, c, h, w = query.shape
+    if tuple(key.shape) != (b * n, c, h, w) or any(tuple(v.shape[0:1] + v.shape[2:]) != (b * n, h, w) for v in values):
+        return False
+    return _attention_fused_plan(b, n, h * w, c, [v.shape[1] for v in values], True, 0) is not None
+
+
+def attention_fused(query, key, values, n, want_mass=True, split=0):
+    """The attention of n_shot = n references (generator.py:298-316) in one streaming launch, forward only, exact fp32: query
+    [b, c, h, w], key [b n, c, h, w], values = one or two reference feature maps [b n, cv, h, w] -> ([attended map [b, cv, h, w] per
+    value map], mass [b, h, w, n] or None), mass = the softmax mass each reference receives per query position.  The [n hw, hw]
+    attention matrix is never formed (csrc/attention.hip); the channels-last memory of the encoders' outputs is read where it lies.
+    split: the number of key ranges per query tile (0: the library's choice for the shape; a finishing launch combines them).  The
+    launch's scratch (fsv_attention_fused_plan) is allocated here, per call; under a captured graph it lives in the graph's pool."""
+    ts = [query, key] + list(values)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise ValueError("attention_fused is forward-only (an input requires grad)")
+    if not 1 <= len(values) <= 2:
+        raise ValueError("attention_fused: one or two value maps, got %d" % len(values))
+    if any(t.dim() != 4 or t.dtype != torch.float32 for t in ts):
+        raise ValueError("attention_fused: 4-D fp32 tensors expected, got %s" % [(tuple(t.shape), t.dtype) for t in ts])
+    query, key = to_nhwc(query.detach()), to_nhwc(key.detach())
+    values = [to_nhwc(v.detach()) for v in values]
+    b, c, h, w = query.shape
+    if tuple(key.shape) != (b * n, c, h, w) or any(tuple(v.shape[0:1] + v.shape[2:]) != (b * n, h, w) for v in values):
+        raise ValueError("attention_fused: query %s, key %s, values %s do not belong to %d references"
+                         % (tuple(query.shape), tuple(key.shape), [tuple(v.shape) for v in values], n))
+    cvs = [v.shape[1] for v in values]
+    plan = _attention_fused_plan(b, n, h * w, c, cvs, want_mass, split)
+    if plan is None:
+        raise lib.FsvError("attention_fused: channels %s are not served (multiples of 4 up to 256): ask attention_fused_supported"
+                           % ([c] + cvs))
+    nsplit, floats = plan
+    outs = [empty_nhwc(b, cv, h, w, query) for cv in cvs]
+    mass = torch.empty((b, h, w, n), dtype=torch.float32, device=query.device) if want_mass else None
+    ws = torch.empty(floats, dtype=torch.float32, device=query.device) if floats else None
+    lib.check_device(query, key, mass, ws, *(values + outs))
+    two = len(values) > 1
+    lib.call("fsv_attention_fused_fwd", lib.ptr(query), lib.ptr(key), lib.ptr(values[0]), lib.ptr(values[1]) if two else None,
+             lib.ptr(outs[0]), lib.ptr(outs[1]) if two else None, lib.ptr(mass), b, n, h * w, c, cvs[0], cvs[1] if two else 0,
+             nsplit, lib.ptr(ws), floats, lib.stream_ptr())
+    return outs, mass
+
+
 # ------------------------------------------------------------------------------------------------ normalisation
 # Cross-replica BatchNorm statistics (opt-in).  The reference's multi-process path makes every BatchNorm of the generator an
 # apex.parallel.SyncBatchNorm (models/networks/normalization.py:15,33,80): statistics over the GLOBAL batch.  Default here is

@@ -517,6 +517,34 @@ int fsv_pool_rows_bwd(const float* drows, float* dx, int N, int H, int W, int C,
  * is not bounded by 2^31.  The forward pass may run in place (y == x). */
 int fsv_softmax_rows_fwd(const float* x, float* y, long long rows, int C, int groups, float* gsum, fsv_stream_t stream);
 int fsv_softmax_rows_bwd(const float* dy, const float* y, float* dx, long long rows, int C, fsv_stream_t stream);
+
+/* ---- streaming few-shot attention (csrc/attention.hip) - generator.py:298-316 without the [N P, P] attention tensor --------------
+ * Forward only, exact fp32 on v_mfma_f32_32x32x2_f32, no atomics: the same bits on every run, whatever FSV_DETERMINISTIC says.
+ *   q    [B][P][C]      query features (the NHWC memory of the atn_query encoder output, P = h w)
+ *   k    [B][N P][C]    key features (the NHWC memory of the atn_key encoder output over the B N references)
+ *   v0   [B][N P][C0]   reference features entering the attention;  v1 [B][N P][C1]: a second map, nullable (o1 / C1 are not read then)
+ *   o0   [B][P][C0], o1 [B][P][C1]: o[b][p] = sum_key a[key] v[b][key], a = softmax over all N P keys of e[key] = <k[b][key], q[b][p]>
+ *   mass [B][P][N], nullable: per query position the sum of a over each reference's P keys (the layout of fsv_softmax_rows_fwd's gsum)
+ * A workgroup owns 128 query positions of one sample and walks tiles of 32 keys in ascending order with an online softmax (running
+ * maximum, denominator and both output accumulators on chip); P is arbitrary (masked tails on both sides), every base is a 64-bit
+ * element offset.  nsplit >= 1: the key tiles are divided over nsplit workgroups per query tile whose partial results a finishing
+ * launch combines in ascending order; nsplit = 0: the library's choice, a function of the shape alone (fsv_attention_fused_plan).
+ * One launch when nsplit is 1 and mass is NULL, one more (the finishing pass) otherwise.  A walk over the keys carries up to eight
+ * 32-channel output tiles, both maps together (C0 = C1 = 128: one walk), and four where C > 128; more tiles than that
+ * (ceil(C0 / 32) + ceil(C1 / 32)) take further walks, one launch each, with the same bits in the shared statistics.
+ * Workspace (the caller's, 16-byte aligned; ws may be NULL when none is needed), in floats and in this order - the partial sums
+ * first, they are read as 16-byte vectors:
+ *     (nsplit > 1 ? nsplit B P (C0 + C1) : 0) + (nsplit > 1 || mass ? 2 nsplit B P : 0) + (mass ? 2 nsplit B P N : 0)
+ * Contract: C, C0, C1 multiples of 4 and at most 256, N P < 2^31 - 64, B <= 65535: FSV_ERR_UNSUPPORTED beyond, nothing launched.
+ * Null q / k / v0 / o0 (o1 with a v1), non-positive B / N / P / C / C0 (C1 with a v1): FSV_ERR_BAD_ARG, before anything else; then
+ * the contract above; then nsplit above 8 or above the ceil(N P / 32) key tiles, or a workspace smaller than the formula:
+ * FSV_ERR_BAD_ARG.  Nothing is launched in any of these cases.
+ * fsv_attention_fused_plan: out[0] = the nsplit the launch would use (the given one when nsplit > 0), out[1] = the workspace in
+ * floats; C1 = 0 for a single map; the same status codes. */
+int fsv_attention_fused_fwd(const float* q, const float* k, const float* v0, const float* v1, float* o0, float* o1, float* mass,
+                            int B, int N, int P, int C, int C0, int C1, int nsplit, float* ws, long long ws_floats,
+                            fsv_stream_t stream);
+int fsv_attention_fused_plan(int B, int N, int P, int C, int C0, int C1, int want_mass, int nsplit, long long* out);
 /* state = {t, 1-beta1^t, 1-beta2^t, lr} on the device; gscale pre-multiplies the gradient (1/world_size) */
 int fsv_adam_step(float* param, const float* grad, float* m, float* v, float* state, long long n, float beta1,
                   float beta2, float eps, float gscale, fsv_stream_t stream);
