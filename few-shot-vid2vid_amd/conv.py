@@ -712,7 +712,8 @@ def conv_wgrad(x, dout, geom, w_shape, per_sample=False, scale=None, force_split
         bm, bn = 64, 64
     label = 'fsv_conv_wgrad_kernel<%dx%d,V%d>' % (bm, bn, 4 if vec4 else 1)
     if (profile.enabled() and cout <= 4 and vec4 and not per_sample and force_tile == 0 and force_split <= 0 and
-            geom.ntaps * (cin >> 2) <= 256 and not narrow_staging_mode() and profile.thin_rule(n * oh * ow, kdim)):
+            geom.ntaps * (cin >> 2) <= 256 and not narrow_staging_mode() and profile.thin_rule(n * oh * ow, kdim) and
+            (os.environ.get('FSV_DETERMINISTIC', '') != '1' or os.environ.get('FSV_CONV_THIN', '') == '2')):
         label = 'fsv_conv_thin_wgrad_kernel<Cout%d>' % cout          # csrc/conv_igemm.hip fsv_conv_wgrad: vector-ALU reduction
     if profile.detail():
         label += ' Kdim%d N%d pix%d z%d' % (geom.ntaps * cin, cout, (oh * ow) if per_sample else n * oh * ow, nb)

@@ -38,6 +38,7 @@ struct AttnFusedP {
   int col0[2];
   float* ml;                   // workspace [nsplit][B][P][2]: maximum, denominator (NULL: not wanted)
   float* mp;                   // workspace [nsplit][B][P][N][2]: a reference's partial mass and the maximum it is relative to
+  float* lse;                  // [B][P]: maximum + log(denominator), written here when nsplit == 1 and nothing is left to finish
   int cv[2], nv[2];            // channels of the two maps, tiles taken from each (second: 0 when absent)
   int B, N, P, C, ncq, nsplit, ntiles;
 };
@@ -209,6 +210,7 @@ __global__ __launch_bounds__(256) void fsv_attn_fused_kernel(AttnFusedP p) {
   if (!wave_live) return;
   flush_mass(g_cur, mass_cur, m_run);
   if (p.ml && lk == 0 && query < P) { p.ml[row * 2] = m_run; p.ml[row * 2 + 1] = l_run; }
+  if (p.lse && lk == 0 && query < P) p.lse[(long long)b * P + query] = m_run + logf(l_run);
 
   // ---- epilogue: normalised when this workgroup saw every key, the raw sums otherwise ------------------------------------------------
   const float inv = p.nsplit == 1 ? 1.f / l_run : 1.f;
@@ -235,6 +237,7 @@ struct AttnFinishP {
   const float* po[2];          // [nsplit][B][P][cv[i]] (nsplit > 1)
   float* o[2];
   float* mass;                 // [B][P][N] or NULL
+  float* lse;                  // [B][P] or NULL: the statistics a backward pass recomputes the probabilities from
   int cv[2];
   int B, N, P, nsplit, ntiles;
   long long rows;              // B P
@@ -259,6 +262,7 @@ __global__ __launch_bounds__(256) void fsv_attn_fused_finish_kernel(AttnFinishP 
       l += w[s] * p.ml[(s * p.rows + row) * 2 + 1];
     }
   }
+  if (p.lse && item == 0) p.lse[row] = m + logf(l);
   if (item < p.nq0 + p.nq1) {
     const int mpi = item < p.nq0 ? 0 : 1;
     const int c = 4 * (mpi ? item - p.nq0 : item);
@@ -329,9 +333,10 @@ extern "C" int fsv_attention_fused_plan(int B, int N, int P, int C, int C0, int 
   return FSV_OK;
 }
 
-extern "C" int fsv_attention_fused_fwd(const float* q, const float* k, const float* v0, const float* v1, float* o0, float* o1,
-                                       float* mass, int B, int N, int P, int C, int C0, int C1, int nsplit, float* ws,
-                                       long long ws_floats, hipStream_t stream) {
+// the one implementation of both forward entry points: lse == NULL is fsv_attention_fused_fwd
+static int fsv_af_forward(const float* q, const float* k, const float* v0, const float* v1, float* o0, float* o1, float* mass,
+                          float* lse, int B, int N, int P, int C, int C0, int C1, int nsplit, float* ws, long long ws_floats,
+                          hipStream_t stream) {
   if (!q || !k || !v0 || !o0 || (v1 && !o1)) return FSV_ERR_BAD_ARG;
   int rc = fsv_af_shape(v1, B, N, P, C, C0, C1);
   if (rc != FSV_OK) return rc;
@@ -375,13 +380,14 @@ extern "C" int fsv_attention_fused_fwd(const float* q, const float* k, const flo
     }
     p.ml = first ? nullptr : ml;                       // (a later walk repeats the first one's statistics bit for bit)
     p.mp = first ? nullptr : mp;
+    p.lse = (first || split > 1 || mass) ? nullptr : lse;      // (otherwise the finishing pass writes it)
     const dim3 grid((P + FSV_AF_BQ - 1) / FSV_AF_BQ, split, B);
     if (C <= 128) FSV_LAUNCH((fsv_attn_fused_kernel<4, true, FSV_AF_NV>), grid, dim3(256), stream, p);
     else FSV_LAUNCH((fsv_attn_fused_kernel<8, false, 4>), grid, dim3(256), stream, p);
   }
   if (split > 1 || mass) {
     AttnFinishP f;
-    f.ml = ml; f.mp = mp; f.po[0] = po0; f.po[1] = po1; f.o[0] = o0; f.o[1] = o1; f.mass = mass;
+    f.ml = ml; f.mp = mp; f.po[0] = po0; f.po[1] = po1; f.o[0] = o0; f.o[1] = o1; f.mass = mass; f.lse = lse;
     f.cv[0] = C0; f.cv[1] = C1;
     f.B = B; f.N = N; f.P = P; f.nsplit = split; f.ntiles = (int)((NP + FSV_AF_BK - 1) / FSV_AF_BK);
     f.rows = rows;
@@ -391,4 +397,16 @@ extern "C" int fsv_attention_fused_fwd(const float* q, const float* k, const flo
     FSV_LAUNCH(fsv_attn_fused_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), stream, f);
   }
   return fsv_check_launch();
+}
+
+extern "C" int fsv_attention_fused_fwd(const float* q, const float* k, const float* v0, const float* v1, float* o0, float* o1,
+                                       float* mass, int B, int N, int P, int C, int C0, int C1, int nsplit, float* ws,
+                                       long long ws_floats, hipStream_t stream) {
+  return fsv_af_forward(q, k, v0, v1, o0, o1, mass, nullptr, B, N, P, C, C0, C1, nsplit, ws, ws_floats, stream);
+}
+
+extern "C" int fsv_attention_fused_fwd_lse(const float* q, const float* k, const float* v0, const float* v1, float* o0, float* o1,
+                                           float* mass, float* lse, int B, int N, int P, int C, int C0, int C1, int nsplit,
+                                           float* ws, long long ws_floats, hipStream_t stream) {
+  return fsv_af_forward(q, k, v0, v1, o0, o1, mass, lse, B, N, P, C, C0, C1, nsplit, ws, ws_floats, stream);
 }

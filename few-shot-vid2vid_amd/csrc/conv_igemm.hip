@@ -2076,8 +2076,10 @@ int fsv_conv_wgrad(const float* in, const float* dout, float* dwt,
   fsv_fill_wgradp(p, in, dout, dwt, N, H, W, Cin, OH, OW, Cout, ntaps, ty, tx, sy, sx, ldw, w_bstride, per_sample, in_up);
   const int nsamp = per_sample ? N : 1;
   if (Cout <= 4 && vec4_ok(Cin) && !per_sample && force_tile == 0 && force_split <= 0 && ntaps * (Cin >> 2) <= 256 &&
-      fsv_conv_thin(p.Mz, p.K)) {
-    // thin-output layers: vector-ALU reduction (fsv_conv_thin_wgrad_kernel), ~512 workgroups, atomics into the zeroed matrix
+      fsv_conv_thin(p.Mz, p.K) && (!fsv_deterministic() || (int)fsv_env("FSV_CONV_THIN", 1) == 2)) {
+    // thin-output layers: vector-ALU reduction (fsv_conv_thin_wgrad_kernel), ~512 workgroups, atomics into the zeroed matrix -
+    // a reduction split across workgroups, so FSV_DETERMINISTIC=1 keeps these layers on the unsplit MFMA launch below (unless
+    // FSV_CONV_THIN=2 asks for this kernel by name)
     p.nsplit = 1;
     if (!prezeroed) (void)hipMemsetAsync(dwt, 0, (size_t)Kpad * ldw * sizeof(float), stream);
     int chunk = fsv_cdiv(p.Mz, 512);

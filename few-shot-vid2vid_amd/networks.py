@@ -592,6 +592,7 @@ class AttentionFused(AttentionBands):
     def __init__(self, b, n, hw, h, w):
         AttentionBands.__init__(self, None, b, n, hw, h, w)
         self.key = None
+        self.grad = False            # taken by the differentiable form (ops.attention_fused_grad)
 
 
 def attention_fused_switch(net=None):
@@ -610,6 +611,24 @@ def attention_fused_switch(net=None):
         f = -1.0
     if f not in (0.0, 1.0):
         raise ValueError("FSV_ATTN_FUSED=%r: 0 or 1 expected" % v)
+    return f == 1.0
+
+
+def attention_fused_grad_switch():
+    """FSV_ATTN_FUSED_GRAD (0 / 1, default 0; read per call): the attention of n_shot > 1 of a DIFFERENTIABLE pass as the streaming
+    forward launch plus the streaming backward kernels (ops.attention_fused_grad) - where autograd is on and the backward serves the
+    shape; ignored otherwise.  Independent of FSV_ATTN_FUSED, which speaks for the no-grad passes only."""
+    if not torch.is_grad_enabled():
+        return False
+    v = os.environ.get('FSV_ATTN_FUSED_GRAD', '')
+    if not v:
+        return False
+    try:
+        f = float(v)
+    except ValueError:
+        f = -1.0
+    if f not in (0.0, 1.0):
+        raise ValueError("FSV_ATTN_FUSED_GRAD=%r: 0 or 1 expected" % v)
     return f == 1.0
 
 
@@ -923,6 +942,10 @@ class FewShotGenerator(nn.Module):
             second = self.__dict__.get('_atn_second', None)
             if ops.attention_fused_serves(b, n, hw, c, [c] + ([second.shape[1]] if second is not None else [])):
                 return self._attention_fused(x, label, label_ref, AttentionFused(b, n, hw, h, w), sink)
+        if attention is None and attention_fused_grad_switch():
+            second = self.__dict__.get('_atn_second', None)
+            if ops.attention_fused_grad_serves(b, n, hw, c, [c] + ([second.shape[1]] if second is not None else [])):
+                return self._attention_fused(x, label, label_ref, AttentionFused(b, n, hw, h, w), None, grad=True)
         plan = attention_band_plan(b, n, hw, h, w) if attention is None else None
         if plan is not None:
             return self._attention_banded(x, label, label_ref, AttentionBands(plan, b, n, hw, h, w), sink)
@@ -966,16 +989,16 @@ class FewShotGenerator(nn.Module):
             atn.second = (second, outs[1])
         return outs[0], atn, atn.atn_vis()
 
-    def _attention_fused(self, x, label, label_ref, atn, sink):
+    def _attention_fused(self, x, label, label_ref, atn, sink, grad=False):
         """attention_module as ONE streaming launch (ops.attention_fused) on the encoders' outputs as they lie in memory: no kmat /
         xmat arrangement, no energy or attention tensor.  An announced second feature map (self._atn_second) rides in the same
-        launch."""
+        launch.  grad: the differentiable pass (FSV_ATTN_FUSED_GRAD) - ops.attention_fused_grad, whose backward streams as well."""
         second = self.__dict__.pop('_atn_second', None)
         key = self.attention_encode(label_ref, 'atn_key')            # [b*n, c, h, w]
         query = self.attention_encode(label, 'atn_query')            # [b, c, h, w]
         vals = [x] + ([second] if second is not None else [])
-        outs, atn.mass = ops.attention_fused(query, key, vals, atn.n)
-        atn.query, atn.key = query, key
+        outs, atn.mass = (ops.attention_fused_grad if grad else ops.attention_fused)(query, key, vals, atn.n)
+        atn.query, atn.key, atn.grad = query, key, grad
         if second is not None:
             atn.second = (second, outs[1])
         if sink is not None:
@@ -990,6 +1013,12 @@ class FewShotGenerator(nn.Module):
         if atn.second is not None and atn.second[0] is x:
             return atn.second[1], atn, atn.atn_vis()
         if isinstance(atn, AttentionFused):        # not announced: a second launch over the same query / key features
+            if atn.grad and atn.query is not None and torch.is_grad_enabled():
+                # the differentiable pass: a second call over the same query / key, autograd adds the two contributions to them
+                if ops.attention_fused_grad_supported(atn.query, atn.key, [x], atn.n):
+                    return ops.attention_fused_grad(atn.query, atn.key, [x], atn.n, want_mass=False)[0][0], atn, atn.atn_vis()
+                raise RuntimeError("fused attention: the backward kernels do not serve a second feature map of %d channels: "
+                                   "announce it before the first call" % x.shape[1])
             if atn.query is None or torch.is_grad_enabled():
                 raise RuntimeError("fused attention: the attention of this pass was not kept for a second feature map")
             if sink is not None:

@@ -1111,6 +1111,111 @@ def attention_fused(query, key, values, n, want_mass=True, split=0):
     return outs, mass
 
 
+def _attention_fused_bwd_plan(b, n, p, c, cvs, split):
+    """(nsplit, workspace floats) of fsv_attention_fused_bwd for this shape, or None when the backward kernels do not serve it"""
+    out = (ctypes.c_longlong * 2)()
+    rc = lib.call_status("fsv_attention_fused_bwd_plan", b, n, p, c, cvs[0], cvs[1] if len(cvs) > 1 else 0, int(split), out)
+    if rc == lib.ENUMS['FSV_ERR_UNSUPPORTED']:
+        return None
+    if rc != 0:
+        raise lib.FsvError("fsv_attention_fused_bwd_plan failed with fsv_status %d" % rc)
+    return int(out[0]), int(out[1])
+
+
+def attention_fused_grad_serves(b, n, p, c, cvs):
+    """whether attention_fused_grad serves these sizes (the answer of the backward's plan entry point; the forward serves whatever
+    the backward does): b samples, n references, p = h w positions, c key / query channels, cvs the one or two value maps' channels"""
+    return (1 <= len(cvs) <= 2 and min(b, n, p, c) >= 1 and _attention_fused_bwd_plan(b, n, p, c, list(cvs), 0) is not None
+            and _attention_fused_plan(b, n, p, c, list(cvs), True, 0) is not None)
+
+
+def attention_fused_grad_supported(query, key, values, n):
+    """whether attention_fused_grad serves these tensors (fp32, one or two value maps, every channel count a multiple of 4 up to
+    128); nothing is launched"""
+    ts = [query, key] + list(values)
+    if not 1 <= len(values) <= 2 or n < 1 or any(t.dim() != 4 or t.dtype != torch.float32 for t in ts):
+        return False
+    b, c, h, w = query.shape
+    if tuple(key.shape) != (b * n, c, h, w) or any(tuple(v.shape[0:1] + v.shape[2:]) != (b * n, h, w) for v in values):
+        return False
+    return attention_fused_grad_serves(b, n, h * w, c, [v.shape[1] for v in values])
+
+
+class _AttentionFusedFn(torch.autograd.Function):
+    """fsv_attention_fused_fwd_lse / fsv_attention_fused_bwd: saved are the operands, the outputs and one float per query"""
+
+    @staticmethod
+    def forward(ctx, n, want_mass, split, query, key, *values):
+        query, key = to_nhwc(query), to_nhwc(key)
+        values = [to_nhwc(v) for v in values]
+        b, c, h, w = query.shape
+        cvs = [v.shape[1] for v in values]
+        nsplit, floats = _attention_fused_plan(b, n, h * w, c, cvs, want_mass, split)
+        outs = [empty_nhwc(b, cv, h, w, query) for cv in cvs]
+        mass = torch.empty((b, h, w, n), dtype=torch.float32, device=query.device) if want_mass else None
+        lse = torch.empty((b, h, w), dtype=torch.float32, device=query.device)
+        ws = torch.empty(floats, dtype=torch.float32, device=query.device) if floats else None
+        lib.check_device(query, key, mass, lse, ws, *(values + outs))
+        two = len(values) > 1
+        lib.call("fsv_attention_fused_fwd_lse", lib.ptr(query), lib.ptr(key), lib.ptr(values[0]), lib.ptr(values[1]) if two else None,
+                 lib.ptr(outs[0]), lib.ptr(outs[1]) if two else None, lib.ptr(mass), lib.ptr(lse), b, n, h * w, c, cvs[0],
+                 cvs[1] if two else 0, nsplit, lib.ptr(ws), floats, lib.stream_ptr())
+        ctx.n, ctx.split, ctx.nv = n, split, len(values)
+        ctx.save_for_backward(query, key, lse, *(values + outs))
+        if mass is None:
+            return tuple(outs)
+        ctx.mark_non_differentiable(mass)
+        return tuple(outs) + (mass,)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        query, key, lse = ctx.saved_tensors[:3]
+        nv = ctx.nv
+        values, outs = list(ctx.saved_tensors[3:3 + nv]), list(ctx.saved_tensors[3 + nv:3 + 2 * nv])
+        b, c, h, w = query.shape
+        cvs = [v.shape[1] for v in values]
+        douts = [to_nhwc(g) if g is not None else zeros_nhwc(b, cv, h, w, query) for g, cv in zip(grads[:nv], cvs)]
+        need = ctx.needs_input_grad[3:]
+        dq = torch.empty_like(query) if need[0] else None
+        dk = torch.empty_like(key) if need[1] else None
+        dvs = [torch.empty_like(v) if need[2 + i] else None for i, v in enumerate(values)]
+        if dq is None and dk is None and all(d is None for d in dvs):
+            return (None,) * (5 + nv)
+        nsplit, floats = _attention_fused_bwd_plan(b, ctx.n, h * w, c, cvs, ctx.split)
+        ws = torch.empty(floats, dtype=torch.float32, device=query.device)
+        lib.check_device(query, key, lse, ws, dq, dk, *(values + outs + douts + dvs))
+        two = nv > 1
+        lib.call("fsv_attention_fused_bwd", lib.ptr(query), lib.ptr(key), lib.ptr(values[0]), lib.ptr(values[1]) if two else None,
+                 lib.ptr(outs[0]), lib.ptr(outs[1]) if two else None, lib.ptr(douts[0]), lib.ptr(douts[1]) if two else None,
+                 lib.ptr(lse), lib.ptr(dq), lib.ptr(dk), lib.ptr(dvs[0]), lib.ptr(dvs[1]) if two else None, b, ctx.n, h * w, c,
+                 cvs[0], cvs[1] if two else 0, nsplit, lib.ptr(ws), floats, lib.stream_ptr())
+        return (None, None, None, dq, dk) + tuple(dvs)
+
+
+def attention_fused_grad(query, key, values, n, want_mass=True, split=0):
+    """attention_fused with a backward pass: the same arguments and results (mass is not differentiable), the forward launch also
+    writes one float per query (the log-sum-exp of its energies), and the backward pass - csrc/attention_bwd.hip - recomputes the
+    probabilities from it tile by tile: no [n hw, hw] tensor in either direction, no kmat / xmat arrangement, exact fp32, no atomics.
+    Channel counts are multiples of 4 up to 128 (attention_fused_grad_supported).  split: the number of key ranges of the forward
+    launch and of the query gradient's launch (0: the library's choice).  The scratch of both calls is allocated per call."""
+    ts = [query, key] + list(values)
+    if not 1 <= len(values) <= 2:
+        raise ValueError("attention_fused_grad: one or two value maps, got %d" % len(values))
+    if any(t.dim() != 4 or t.dtype != torch.float32 for t in ts):
+        raise ValueError("attention_fused_grad: 4-D fp32 tensors expected, got %s" % [(tuple(t.shape), t.dtype) for t in ts])
+    b, c, h, w = query.shape
+    if tuple(key.shape) != (b * n, c, h, w) or any(tuple(v.shape[0:1] + v.shape[2:]) != (b * n, h, w) for v in values):
+        raise ValueError("attention_fused_grad: query %s, key %s, values %s do not belong to %d references"
+                         % (tuple(query.shape), tuple(key.shape), [tuple(v.shape) for v in values], n))
+    cvs = [v.shape[1] for v in values]
+    if (_attention_fused_bwd_plan(b, n, h * w, c, cvs, split) is None
+            or _attention_fused_plan(b, n, h * w, c, cvs, want_mass, split) is None):
+        raise lib.FsvError("attention_fused_grad: channels %s are not served (multiples of 4 up to 128): ask "
+                           "attention_fused_grad_supported" % ([c] + cvs))
+    res = _AttentionFusedFn.apply(n, bool(want_mass), int(split), query, key, *values)
+    return list(res[:len(values)]), (res[len(values)] if want_mass else None)
+
+
 # ------------------------------------------------------------------------------------------------ normalisation
 # Cross-replica BatchNorm statistics (opt-in).  The reference's multi-process path makes every BatchNorm of the generator an
 # apex.parallel.SyncBatchNorm (models/networks/normalization.py:15,33,80): statistics over the GLOBAL batch.  Default here is

@@ -545,6 +545,35 @@ int fsv_attention_fused_fwd(const float* q, const float* k, const float* v0, con
                             int B, int N, int P, int C, int C0, int C1, int nsplit, float* ws, long long ws_floats,
                             fsv_stream_t stream);
 int fsv_attention_fused_plan(int B, int N, int P, int C, int C0, int C1, int want_mass, int nsplit, long long* out);
+/* ---- the differentiable form (csrc/attention.hip, csrc/attention_bwd.hip): exact fp32 on v_mfma_f32_32x32x2_f32, no atomics, the
+ * same bits on every run whatever FSV_DETERMINISTIC says; the same NHWC-in-place operands, 64-bit bases, masked tails for any P.
+ * fsv_attention_fused_fwd_lse: fsv_attention_fused_fwd (one shared implementation: the same arguments, bounds, status codes,
+ * workspace formula - fsv_attention_fused_plan - and launch counts; o0 / o1 / mass have the same bits) that also writes
+ *   lse  [B][P], nullable: per query the running maximum plus the log of the softmax denominator
+ * from the kernel's own epilogue when one workgroup walks all keys and no mass is wanted, from the finishing launch otherwise.
+ * fsv_attention_fused_bwd: with p = exp(<k[key], q[query]> - lse[query]) recomputed tile by tile (never positive exponents) and the
+ * cotangents do0 [B][P][C0], do1 [B][P][C1] of o0 / o1 (o1 / do1 are read only with a v1):
+ *   delta[query] = sum_c do0 o0 + sum_c do1 o1,   dp = <do0[query], v0[key]> + <do1[query], v1[key]>,   ds = p (dp - delta[query])
+ *   dq [B][P][C] = sum_key ds k[key]      dk [B][N P][C] = sum_query ds q[query]      dv_i [B][N P][Ci] = sum_query p do_i[query]
+ * Each of dq / dk / dv0 / dv1 is nullable (a gradient the caller does not need; what is produced has the same bits whichever others
+ * are asked for); at least one must be given, dv1 only with a v1.  Launches: delta (one wave per query, when dq or dk is wanted);
+ * dq by a query-owning kernel (128 queries per workgroup, key tiles of 32 through LDS, the keys in nsplit ranges whose partial
+ * sums one more launch adds in ascending order - nsplit as in the forward, 0: the library's choice); dv0 / dv1 and dk by two
+ * key-owning launches (128 keys per workgroup, query tiles of 32 through LDS, every query in ascending order, no split).
+ * Workspace (the caller's, 16-byte aligned), in floats: 4 ceil(B P / 4) + (nsplit > 1 ? nsplit B P C : 0) - a function of the shape
+ * alone, whichever outputs are asked for (fsv_attention_fused_bwd_plan: out[0] = nsplit, out[1] = floats; C1 = 0: a single map).
+ * Contract: C, C0, C1 multiples of 4 and at most 128 (the production shape), N P < 2^31 - 64, B <= 65535: FSV_ERR_UNSUPPORTED beyond,
+ * nothing launched.  Null q / k / v0 / o0 / do0 / lse (o1 / do1 with a v1), a dv1 without a v1, all four outputs null, non-positive
+ * B / N / P / C / C0 (C1 with a v1): FSV_ERR_BAD_ARG, before anything else; then the contract; then nsplit above 8 or above the
+ * ceil(N P / 32) key tiles, a null or too small workspace: FSV_ERR_BAD_ARG. */
+int fsv_attention_fused_fwd_lse(const float* q, const float* k, const float* v0, const float* v1, float* o0, float* o1, float* mass,
+                                float* lse, int B, int N, int P, int C, int C0, int C1, int nsplit, float* ws, long long ws_floats,
+                                fsv_stream_t stream);
+int fsv_attention_fused_bwd(const float* q, const float* k, const float* v0, const float* v1, const float* o0, const float* o1,
+                            const float* do0, const float* do1, const float* lse, float* dq, float* dk, float* dv0, float* dv1,
+                            int B, int N, int P, int C, int C0, int C1, int nsplit, float* ws, long long ws_floats,
+                            fsv_stream_t stream);
+int fsv_attention_fused_bwd_plan(int B, int N, int P, int C, int C0, int C1, int nsplit, long long* out);
 /* state = {t, 1-beta1^t, 1-beta2^t, lr} on the device; gscale pre-multiplies the gradient (1/world_size) */
 int fsv_adam_step(float* param, const float* grad, float* m, float* v, float* state, long long n, float beta1,
                   float beta2, float eps, float gscale, fsv_stream_t stream);
