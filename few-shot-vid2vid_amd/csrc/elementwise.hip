@@ -158,22 +158,78 @@ __global__ void fsv_adam_tick_kernel(float* state, float beta1, float beta2) {
   }
 }
 
+// One element's update.  B1ZERO (beta1 == 0, the reference's TTUR setting FlatAdam(betas=(0.0, 0.999))): the first moment IS the
+// scaled gradient, so m is written and never read - 24 instead of 28 bytes per parameter.  0 * m + 1 * g == g as a value for every
+// finite m; only the sign of a zero can differ in the stored m (and in a parameter that is exactly -0 under a gradient that is
+// exactly -0), v and every other parameter are bit-identical.  A non-finite m (it would have been a non-finite gradient one step
+// earlier, which already destroyed the parameters) is NOT carried forward in this form.
+template <bool B1ZERO>
+__device__ __forceinline__ void fsv_adam_elem(float& p, float graw, float& m, float& v, float beta1, float beta2, float eps,
+                                              float gscale, float step_size, float rbc2) {
+  const float g = graw * gscale;
+  const float mi = B1ZERO ? g : beta1 * m + (1.f - beta1) * g;
+  const float vi = beta2 * v + (1.f - beta2) * g * g;
+  m = mi; v = vi;
+  const float denom = sqrtf(vi) * rbc2 + eps;
+  p = p - step_size * (mi / denom);
+}
+
+// Elements [head, head + 4 * nvec) go as 16-byte accesses (the host chose head so that all four pointers are 16-byte aligned
+// there: the four arrays of a range share their misalignment), the head (< 4) and the tail (< 4) elements one by one.
+template <bool B1ZERO>
+__device__ __forceinline__ void fsv_adam_range(float* param, const float* grad, float* m, float* v, long long n, int head,
+                                               long long nvec, float beta1, float beta2, float eps, float gscale,
+                                               float step_size, float rbc2) {
+  const long long tid = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = tid; i < nvec; i += stride) {
+    const long long o = head + i * 4;
+    float4 pv = *reinterpret_cast<const float4*>(param + o);
+    const float4 gv = *reinterpret_cast<const float4*>(grad + o);
+    float4 vv = *reinterpret_cast<const float4*>(v + o);
+    float4 mv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!B1ZERO) mv = *reinterpret_cast<const float4*>(m + o);
+    fsv_adam_elem<B1ZERO>(pv.x, gv.x, mv.x, vv.x, beta1, beta2, eps, gscale, step_size, rbc2);
+    fsv_adam_elem<B1ZERO>(pv.y, gv.y, mv.y, vv.y, beta1, beta2, eps, gscale, step_size, rbc2);
+    fsv_adam_elem<B1ZERO>(pv.z, gv.z, mv.z, vv.z, beta1, beta2, eps, gscale, step_size, rbc2);
+    fsv_adam_elem<B1ZERO>(pv.w, gv.w, mv.w, vv.w, beta1, beta2, eps, gscale, step_size, rbc2);
+    *reinterpret_cast<float4*>(m + o) = mv;
+    *reinterpret_cast<float4*>(v + o) = vv;
+    *reinterpret_cast<float4*>(param + o) = pv;
+  }
+  // scalar elements: [0, head) and [head + 4 nvec, n) - at most 3 + 3 unless the host found no common alignment (nvec == 0)
+  const long long body_end = head + nvec * 4;
+  const long long nscalar = n - nvec * 4;
+  for (long long k = tid; k < nscalar; k += stride) {
+    const long long i = k < head ? k : body_end + (k - head);
+    float pi = param[i], mi = B1ZERO ? 0.f : m[i], vi = v[i];
+    fsv_adam_elem<B1ZERO>(pi, grad[i], mi, vi, beta1, beta2, eps, gscale, step_size, rbc2);
+    m[i] = mi; v[i] = vi; param[i] = pi;
+  }
+}
+
 __global__ __launch_bounds__(256) void fsv_adam_kernel(float* param, const float* grad, float* m, float* v,
-                                                       const float* state, long long n, float beta1, float beta2,
-                                                       float eps, float gscale) {
+                                                       const float* state, long long n, int head, long long nvec, float beta1,
+                                                       float beta2, float eps, float gscale) {
   const float bc1 = state[1], bc2 = state[2], lr = state[3];
   const float step_size = lr / bc1;
   const float rbc2 = 1.f / sqrtf(bc2);
-  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long stride = (long long)gridDim.x * 256;
-  for (; i < n; i += stride) {
-    float g = grad[i] * gscale;
-    float mi = beta1 * m[i] + (1.f - beta1) * g;
-    float vi = beta2 * v[i] + (1.f - beta2) * g * g;
-    m[i] = mi; v[i] = vi;
-    float denom = sqrtf(vi) * rbc2 + eps;
-    param[i] = param[i] - step_size * (mi / denom);
-  }
+  if (beta1 == 0.f) fsv_adam_range<true>(param, grad, m, v, n, head, nvec, beta1, beta2, eps, gscale, step_size, rbc2);       // uniform
+  else fsv_adam_range<false>(param, grad, m, v, n, head, nvec, beta1, beta2, eps, gscale, step_size, rbc2);
+}
+
+// head / nvec of fsv_adam_kernel: param, grad, m, v of a range start at the same element offset of 16-byte-aligned flat buffers
+// (a slice that starts at any element), so one scalar head aligns all four; pointers that do not agree go element by element
+static inline void fsv_launch_adam(float* param, const float* grad, float* m, float* v, const float* state, long long n,
+                                   float beta1, float beta2, float eps, float gscale, hipStream_t stream) {
+  const uintptr_t a = (uintptr_t)param & 15;
+  const bool same = ((uintptr_t)grad & 15) == a && ((uintptr_t)m & 15) == a && ((uintptr_t)v & 15) == a && (a & 3) == 0;
+  long long head = same ? (long long)(((16 - a) & 15) / 4) : n;
+  if (head > n) head = n;
+  const long long nvec = (n - head) / 4;
+  const long long units = nvec > n - nvec * 4 ? nvec : n - nvec * 4;
+  FSV_LAUNCH(fsv_adam_kernel, dim3(fsv_grid_for(units)), dim3(256), stream, param, grad, m, v, state, n, (int)head, nvec, beta1,
+             beta2, eps, gscale);
 }
 
 extern "C" {
@@ -270,8 +326,7 @@ int fsv_adam_step(float* param, const float* grad, float* m, float* v, float* st
                   float beta2, float eps, float gscale, hipStream_t stream) {
   if (!param || !grad || !m || !v || !state || n < 0) return FSV_ERR_BAD_ARG;
   FSV_LAUNCH(fsv_adam_tick_kernel, dim3(1), dim3(64), stream, state, beta1, beta2);
-  FSV_LAUNCH(fsv_adam_kernel, dim3(fsv_grid_for(n / 4 + 1)), dim3(256), stream, param, grad, m, v, (const float*)state, n,
-             beta1, beta2, eps, gscale);
+  fsv_launch_adam(param, grad, m, v, (const float*)state, n, beta1, beta2, eps, gscale, stream);
   return fsv_check_launch();
 }
 
@@ -283,8 +338,7 @@ int fsv_adam_step_range(float* param, const float* grad, float* m, float* v, flo
   if (!param || !grad || !m || !v || !state || n < 0) return FSV_ERR_BAD_ARG;
   if (tick) FSV_LAUNCH(fsv_adam_tick_kernel, dim3(1), dim3(64), stream, state, beta1, beta2);
   if (n > 0)
-    FSV_LAUNCH(fsv_adam_kernel, dim3(fsv_grid_for(n / 4 + 1)), dim3(256), stream, param, grad, m, v, (const float*)state, n,
-               beta1, beta2, eps, gscale);
+    fsv_launch_adam(param, grad, m, v, (const float*)state, n, beta1, beta2, eps, gscale, stream);
   return fsv_check_launch();
 }
 

@@ -15,7 +15,7 @@
 // One template serves the four reductions of this file:
 //   STATS  : (sum x, sum x^2)                           forward statistics
 //   STATS64: the same with fp64 accumulators in the thread and in LDS (fsv_norm_sums: sums that leave the device)
-//   BWD    : (sum d, sum d * xhat), d = dy * act'(y)     normalisation backward
+//   BWD    : (sum d, sum d * xhat), d = dy * act'(y)     normalisation backward (y == null: the slope from v, see fsv_norm_pre)
 //   COLSUM : (sum x, -)                                  bias gradients
 // Grid = (pixel chunks, channel slabs, groups).  A block covers TX column units (float4 = 4 channels when
 // C % 4 == 0) x TY = 256/TX rows in flight; every thread keeps 4 independent row streams so that >= 4 vector loads
@@ -58,12 +58,33 @@ __device__ __forceinline__ float fsv_act_grad(float dy, float y, int act) {
   return dy;
 }
 
+// The pre-activation of a normalisation site, v = ((x - mean) * rstd) * w + b (xhat alone without the affine pair).  The forward
+// kernels and the y-free backward (fsv_norm_bwd_fused with y == null) all take v from HERE: the backward picks the slope of
+// LeakyReLU / ReLU by v > 0 where the forward picked the branch by v > 0, so both must round v alike.  The forward has always
+// compiled to subtract, multiply, multiply, add (the library is built with -ffp-contract=off, GPU and emulator alike:
+// v_sub_f32, v_mul_f32, v_mul_f32, v_add_f32 in fsv_norm_apply4_kernel); the pragma pins that form to this function whatever the
+// command line says.  A fused multiply-add in one of the two places would flip the slope of elements within one rounding of
+// the kink (tests/c1_kink.py: one such element moved a layer's weight gradient by 3.6 %).
+__device__ __forceinline__ float fsv_norm_pre(float x, float mean, float rstd, bool affine, float w, float b) {
+#pragma clang fp contract(off)
+  const float xh = (x - mean) * rstd;
+  return affine ? xh * w + b : xh;
+}
+
+// y > 0 exactly when v > 0 for these three (y = v, 0.2 v, 0.1 v or 0; a negative denormal v may flush to -0, still not > 0; NaN
+// compares false on both sides): fsv_act_grad(dy, v, act) is fsv_act_grad(dy, y, act)
+static inline bool fsv_act_sign_from_pre(int act) {
+  return act == FSV_ACT_LRELU || act == FSV_ACT_LRELU01 || act == FSV_ACT_RELU;
+}
+
 struct RedP {
   const float* a;       // STATS/COLSUM: x;  BWD: dy
-  const float* y;       // BWD: activated output (may be null when act == none)
+  const float* y;       // BWD: activated output (may be null when act == none, or with w / b below)
   const float* x;       // BWD: normalisation input
   const float* mean;
   const float* rstd;
+  const float* w;       // BWD with y == null and an activation: the forward's affine pair (both null: non-affine site) - the
+  const float* b;       //   slope comes from v = fsv_norm_pre(x, ...) instead of y
   double* part;
   int P, C, CU, TX, TY, rows_per_blk, nchunks, act;
   // fused second stage (counter != null): the workgroup that finishes last on a channel slab sums the partials of that
@@ -77,7 +98,9 @@ struct RedP {
 
 __device__ __forceinline__ void fsv_sum_chunks(const double* part, int g, int c, int C, int nchunks, double& a, double& b);
 
-template <int MODE, int V>
+// FROMX (BWD only; the host takes it for y == null with an activation): the slope from the recomputed pre-activation - this
+// instance holds no y registers and issues no y loads, the other one is the kernel as it was
+template <int MODE, int V, bool FROMX = false>
 __global__ __launch_bounds__(256) void fsv_red2_kernel(RedP p) {
   constexpr bool WIDE = MODE == FSV_RED_STATS64;
   typedef typename std::conditional<WIDE, double, float>::type acc_t;
@@ -90,14 +113,20 @@ __global__ __launch_bounds__(256) void fsv_red2_kernel(RedP p) {
   const int r1 = (r0 + p.rows_per_blk < p.P) ? r0 + p.rows_per_blk : p.P;
   const long long goff = (long long)g * p.P * p.C;
   acc_t s1[V], s2[V];
-  float mu[V], rs[V];
+  float mu[V], rs[V], wv[V], bv[V];
+  constexpr bool from_x = MODE == FSV_RED_BWD && FROMX;
+  const bool affine = from_x && p.w != nullptr;                                          // uniform
 #pragma unroll
-  for (int j = 0; j < V; ++j) { s1[j] = 0; s2[j] = 0; mu[j] = 0.f; rs[j] = 1.f; }
+  for (int j = 0; j < V; ++j) { s1[j] = 0; s2[j] = 0; mu[j] = 0.f; rs[j] = 1.f; wv[j] = 1.f; bv[j] = 0.f; }
   if (active) {
     const int c0 = cu * V;
     if (MODE == FSV_RED_BWD) {
 #pragma unroll
       for (int j = 0; j < V; ++j) { mu[j] = p.mean[g * p.C + c0 + j]; rs[j] = p.rstd[g * p.C + c0 + j]; }
+      if (from_x && affine) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) { wv[j] = p.w[c0 + j]; bv[j] = p.b[c0 + j]; }
+      }
     }
     for (int r = r0 + ty; r < r1; r += p.TY * 4) {
       float va[4][V], vy[4][V], vx[4][V];
@@ -112,12 +141,14 @@ __global__ __launch_bounds__(256) void fsv_red2_kernel(RedP p) {
           if (MODE == FSV_RED_BWD) {
             float4 tx4 = ok ? *reinterpret_cast<const float4*>(p.x + off) : make_float4(0.f, 0.f, 0.f, 0.f);
             vx[u][0] = tx4.x; vx[u][1] = tx4.y; vx[u][2] = tx4.z; vx[u][3] = tx4.w;
-            float4 ty4 = (ok && p.y) ? *reinterpret_cast<const float4*>(p.y + off) : make_float4(0.f, 0.f, 0.f, 0.f);
-            vy[u][0] = ty4.x; vy[u][1] = ty4.y; vy[u][2] = ty4.z; vy[u][3] = ty4.w;
+            if (!from_x) {
+              float4 ty4 = (ok && p.y) ? *reinterpret_cast<const float4*>(p.y + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+              vy[u][0] = ty4.x; vy[u][1] = ty4.y; vy[u][2] = ty4.z; vy[u][3] = ty4.w;
+            }
           }
         } else {
           va[u][0] = ok ? p.a[off] : 0.f;
-          if (MODE == FSV_RED_BWD) { vx[u][0] = ok ? p.x[off] : 0.f; vy[u][0] = (ok && p.y) ? p.y[off] : 0.f; }
+          if (MODE == FSV_RED_BWD) { vx[u][0] = ok ? p.x[off] : 0.f; vy[u][0] = (ok && p.y && !from_x) ? p.y[off] : 0.f; }
         }
         if (MODE == FSV_RED_BWD && !ok) {
 #pragma unroll
@@ -132,7 +163,8 @@ __global__ __launch_bounds__(256) void fsv_red2_kernel(RedP p) {
           else if (WIDE) { const acc_t w = va[u][j]; s1[j] += w; s2[j] += w * w; }
           else if (MODE == FSV_RED_COLSUM) { s1[j] += va[u][j]; }
           else {
-            float d = fsv_act_grad(va[u][j], vy[u][j], p.act);
+            const float ys = from_x ? fsv_norm_pre(vx[u][j], mu[j], rs[j], affine, wv[j], bv[j]) : vy[u][j];
+            float d = fsv_act_grad(va[u][j], ys, p.act);
             s1[j] += d; s2[j] += d * ((vx[u][j] - mu[j]) * rs[j]);
           }
         }
@@ -258,6 +290,11 @@ template <int MODE>
 static inline void fsv_launch_red(const RedPlan& pl, RedP p, int G, hipStream_t stream) {
   p.CU = pl.CU; p.TX = pl.TX; p.TY = pl.TY; p.rows_per_blk = pl.rows_per_blk; p.nchunks = pl.nchunks;
   dim3 grid(pl.nchunks, pl.nslabs, G);
+  if (MODE == FSV_RED_BWD && !p.y && p.act != FSV_ACT_NONE) {          // the entry point has checked act and the w / b pair
+    if (pl.V == 4) FSV_LAUNCH((fsv_red2_kernel<MODE, 4, true>), grid, dim3(256), stream, p);
+    else FSV_LAUNCH((fsv_red2_kernel<MODE, 1, true>), grid, dim3(256), stream, p);
+    return;
+  }
   if (pl.V == 4) FSV_LAUNCH((fsv_red2_kernel<MODE, 4>), grid, dim3(256), stream, p);
   else FSV_LAUNCH((fsv_red2_kernel<MODE, 1>), grid, dim3(256), stream, p);
 }
@@ -307,8 +344,8 @@ __global__ __launch_bounds__(256) void fsv_norm_apply_kernel(const float* x, con
   for (; i < total; i += stride) {
     int c = (int)(i % C);
     int g = (int)(i / PC);
-    float xh = (x[i] - mean[g * C + c]) * rstd[g * C + c];
-    float v = w ? xh * w[c] + b[c] : xh;
+    const bool affine = w != nullptr;
+    float v = fsv_norm_pre(x[i], mean[g * C + c], rstd[g * C + c], affine, affine ? w[c] : 1.f, affine ? b[c] : 0.f);
     y[i] = fsv_act(v, act);
   }
 }
@@ -326,11 +363,11 @@ __global__ __launch_bounds__(256) void fsv_norm_apply4_kernel(const float* x, co
     const unsigned gc = g * C4 * 4u + c;
     const float4 xv = *reinterpret_cast<const float4*>(x + (size_t)i * 4);
     const float4 mu = *reinterpret_cast<const float4*>(mean + gc), rs = *reinterpret_cast<const float4*>(rstd + gc);
-    float4 v = make_float4((xv.x - mu.x) * rs.x, (xv.y - mu.y) * rs.y, (xv.z - mu.z) * rs.z, (xv.w - mu.w) * rs.w);
-    if (w) {
-      const float4 wv = *reinterpret_cast<const float4*>(w + c), bv = *reinterpret_cast<const float4*>(b + c);
-      v = make_float4(v.x * wv.x + bv.x, v.y * wv.y + bv.y, v.z * wv.z + bv.z, v.w * wv.w + bv.w);
-    }
+    const bool affine = w != nullptr;
+    float4 wv = make_float4(1.f, 1.f, 1.f, 1.f), bv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (affine) { wv = *reinterpret_cast<const float4*>(w + c); bv = *reinterpret_cast<const float4*>(b + c); }
+    const float4 v = make_float4(fsv_norm_pre(xv.x, mu.x, rs.x, affine, wv.x, bv.x), fsv_norm_pre(xv.y, mu.y, rs.y, affine, wv.y, bv.y),
+                                 fsv_norm_pre(xv.z, mu.z, rs.z, affine, wv.z, bv.z), fsv_norm_pre(xv.w, mu.w, rs.w, affine, wv.w, bv.w));
     const float4 o = make_float4(fsv_act(v.x, act), fsv_act(v.y, act), fsv_act(v.z, act), fsv_act(v.w, act));
     *reinterpret_cast<float4*>(y + (size_t)i * 4) = o;
     if (yh) {                   // uniform: the half side output (fsv_common.h)
@@ -363,9 +400,11 @@ __global__ __launch_bounds__(256) void fsv_norm_bwd_final_kernel(const double* p
 }
 
 // dx = w * rstd * (dyp - s1/P - xhat * s2/P)
+// from_x (uniform; the host sets it only for y == null with LeakyReLU / ReLU): the slope of dyp = dy * act' comes from the
+// recomputed pre-activation, b being the forward's bias (null with w for a non-affine site)
 __global__ __launch_bounds__(256) void fsv_norm_bwd_apply_kernel(const float* dy, const float* y, const float* x,
                                                                  const float* mean, const float* rstd, const float* w,
-                                                                 const float* s1, const float* s2, float* dx,
+                                                                 const float* b, int from_x, const float* s1, const float* s2, float* dx,
                                                                  long long total, long long PC, int C, int P, int act,
                                                                  int fixed_stats) {
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -377,36 +416,50 @@ __global__ __launch_bounds__(256) void fsv_norm_bwd_apply_kernel(const float* dy
     int gc = g * C + c;
     float rs = rstd[gc];
     float xh = (x[i] - mean[gc]) * rs;
-    float d = fsv_act_grad(dy[i], y ? y[i] : 0.f, act);
     float wv = w ? w[c] : 1.f;
+    float ys = from_x ? fsv_norm_pre(x[i], mean[gc], rs, w != nullptr, wv, w ? b[c] : 0.f) : (y ? y[i] : 0.f);
+    float d = fsv_act_grad(dy[i], ys, act);
     // fixed_stats: eval-mode normalisation (running statistics are constants): only the affine scale remains
     dx[i] = fixed_stats ? wv * rs * d : wv * rs * (d - s1[gc] * invP - xh * (s2[gc] * invP));
   }
 }
 
-// four consecutive channels per work-item (C % 4 == 0, fewer than 2^31 elements)
+// four consecutive channels per work-item (C % 4 == 0, fewer than 2^31 elements).  FROMX: the slope from the recomputed
+// pre-activation - that instance has no y operand at all.  The per-channel quads (mean, rstd, w, b, s1, s2: 16-byte loads like the
+// forward's) are all requested before the first value is used: one memory round trip per work-item.
+template <bool FROMX>
 __global__ __launch_bounds__(256) void fsv_norm_bwd_apply4_kernel(const float* dy, const float* y, const float* x,
                                                                   const float* mean, const float* rstd, const float* w,
-                                                                  const float* s1, const float* s2, float* dx,
-                                                                  unsigned total4, unsigned PC4, unsigned C4, int P, int act,
+                                                                  const float* b, const float* s1, const float* s2,
+                                                                  float* dx, unsigned total4, unsigned PC4, unsigned C4, int P, int act,
                                                                   int fixed_stats, _Float16* dxh) {
   const unsigned stride = gridDim.x * 256u;
   const float invP = 1.0f / (float)P;
+  const bool affine = w != nullptr;
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total4; i += stride) {
     const unsigned c = (i % C4) * 4u, g = i / PC4;
     const unsigned gc = g * C4 * 4u + c;
     const size_t o = (size_t)i * 4;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 xv = *reinterpret_cast<const float4*>(x + o), dv = *reinterpret_cast<const float4*>(dy + o);
-    const float4 yv = y ? *reinterpret_cast<const float4*>(y + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 yv = (!FROMX && y) ? *reinterpret_cast<const float4*>(y + o) : zero4;
+    const float4 mu4 = *reinterpret_cast<const float4*>(mean + gc), rs4 = *reinterpret_cast<const float4*>(rstd + gc);
+    const float4 w4 = affine ? *reinterpret_cast<const float4*>(w + c) : make_float4(1.f, 1.f, 1.f, 1.f);
+    const float4 b4 = (FROMX && affine) ? *reinterpret_cast<const float4*>(b + c) : zero4;
+    const float4 p4 = fixed_stats ? zero4 : *reinterpret_cast<const float4*>(s1 + gc);
+    const float4 q4 = fixed_stats ? zero4 : *reinterpret_cast<const float4*>(s2 + gc);
     const float xa[4] = {xv.x, xv.y, xv.z, xv.w}, da[4] = {dv.x, dv.y, dv.z, dv.w}, ya[4] = {yv.x, yv.y, yv.z, yv.w};
+    const float ma[4] = {mu4.x, mu4.y, mu4.z, mu4.w}, ra[4] = {rs4.x, rs4.y, rs4.z, rs4.w}, wa[4] = {w4.x, w4.y, w4.z, w4.w};
+    const float ba[4] = {b4.x, b4.y, b4.z, b4.w}, pa[4] = {p4.x, p4.y, p4.z, p4.w}, qa[4] = {q4.x, q4.y, q4.z, q4.w};
     float r[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float rs = rstd[gc + j];
-      const float xh = (xa[j] - mean[gc + j]) * rs;
-      const float d = fsv_act_grad(da[j], ya[j], act);
-      const float wv = w ? w[c + j] : 1.f;
-      r[j] = fixed_stats ? wv * rs * d : wv * rs * (d - s1[gc + j] * invP - xh * (s2[gc + j] * invP));
+      const float rs = ra[j], mu = ma[j];
+      const float xh = (xa[j] - mu) * rs;
+      const float wv = wa[j];
+      const float ys = FROMX ? fsv_norm_pre(xa[j], mu, rs, affine, wv, ba[j]) : ya[j];
+      const float d = fsv_act_grad(da[j], ys, act);
+      r[j] = fixed_stats ? wv * rs * d : wv * rs * (d - pa[j] * invP - xh * (qa[j] * invP));
     }
     *reinterpret_cast<float4*>(dx + o) = make_float4(r[0], r[1], r[2], r[3]);
     if (dxh) {
@@ -537,7 +590,7 @@ int fsv_norm_stats_rep(const float* x, double* workspace, float* mean, float* rs
   if (!x || !workspace || !mean || !rstd || G < 1 || P < 1 || C < 1 || rep < 1) return FSV_ERR_BAD_ARG;
   RedPlan pl = fsv_red_plan(G, P, C);
   const int nchunks = pl.nchunks;
-  RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.part = workspace;
+  RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.w = nullptr; rp.b = nullptr; rp.part = workspace;
   rp.P = P; rp.C = C; rp.act = 0; fsv_red_no_tail(rp);
   fsv_launch_red<FSV_RED_STATS>(pl, rp, G, stream);
   FSV_LAUNCH(fsv_stats_final_kernel, dim3(fsv_cdiv(G * C, 4)), dim3(256), stream, (const double*)workspace, mean, rstd,
@@ -569,18 +622,22 @@ static inline bool fsv_ew_vec4(long long total, int C) {
 }
 
 static inline void fsv_launch_bwd_apply(const float* dy, const float* y, const float* x, const float* mean, const float* rstd,
-                                        const float* w, const float* s1, const float* s2, float* dx, long long total,
+                                        const float* w, const float* b, const float* s1, const float* s2, float* dx, long long total,
                                         long long PC, int C, int P, int act, int fixed_stats, void* dx_half,
                                         hipStream_t stream) {
   // (a half side output only exists in the four-channels-per-work-item form: fsv_half_side_ok was checked by the entry point)
   const bool v4 = dx_half ? true : fsv_ew_vec4(total, C);
   _Float16* dxh = reinterpret_cast<_Float16*>(dx_half);
-  if (v4) {
-    FSV_LAUNCH(fsv_norm_bwd_apply4_kernel, dim3(fsv_ew_grid(total / 4)), dim3(256), stream, dy, y, x, mean, rstd, w, s1, s2, dx,
-               (unsigned)(total / 4), (unsigned)(PC / 4), (unsigned)(C / 4), P, act, fixed_stats, dxh);
+  const int from_x = (!y && act != FSV_ACT_NONE) ? 1 : 0;
+  if (v4 && from_x) {
+    FSV_LAUNCH((fsv_norm_bwd_apply4_kernel<true>), dim3(fsv_ew_grid(total / 4)), dim3(256), stream, dy, y, x, mean, rstd, w, b, s1,
+               s2, dx, (unsigned)(total / 4), (unsigned)(PC / 4), (unsigned)(C / 4), P, act, fixed_stats, dxh);
+  } else if (v4) {
+    FSV_LAUNCH((fsv_norm_bwd_apply4_kernel<false>), dim3(fsv_ew_grid(total / 4)), dim3(256), stream, dy, y, x, mean, rstd, w, b, s1,
+               s2, dx, (unsigned)(total / 4), (unsigned)(PC / 4), (unsigned)(C / 4), P, act, fixed_stats, dxh);
   } else {
-    FSV_LAUNCH(fsv_norm_bwd_apply_kernel, dim3(fsv_ew_grid(total)), dim3(256), stream, dy, y, x, mean, rstd, w, s1, s2, dx,
-               total, PC, C, P, act, fixed_stats);
+    FSV_LAUNCH(fsv_norm_bwd_apply_kernel, dim3(fsv_ew_grid(total)), dim3(256), stream, dy, y, x, mean, rstd, w, b, from_x, s1, s2,
+               dx, total, PC, C, P, act, fixed_stats);
   }
 }
 
@@ -609,32 +666,47 @@ int fsv_norm_apply(const float* x, const float* mean, const float* rstd, const f
   return fsv_check_launch();
 }
 
-// dy: upstream gradient w.r.t. the activated output y (y may be null when act == none).  Produces dx and, when
-// dw/db are non-null, the affine parameter gradients.  s1/s2: [G*C] scratch.
-int fsv_norm_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* w,
-                 double* workspace, float* s1, float* s2, float* dx, float* dw, float* db, int G, int P, int C, int act,
-                 int fixed_stats, void* dx_half, hipStream_t stream) {
+// where the slope of the activation comes from: y when it is given; without y, nothing to pick for act == none, and for
+// LeakyReLU / ReLU the sign of the recomputed pre-activation - then b (the forward's bias) must be set exactly when w is
+static inline bool fsv_norm_bwd_slope_ok(const float* y, const float* w, const float* b, int act) {
+  if (y || act == FSV_ACT_NONE) return true;
+  return fsv_act_sign_from_pre(act) && ((w != nullptr) == (b != nullptr));
+}
+
+// the two-launch sums + apply behind fsv_norm_bwd (b == null) and behind fsv_norm_bwd_fused above the ticket threshold
+static int fsv_norm_bwd_two(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* w,
+                            const float* b, double* workspace, float* s1, float* s2, float* dx, float* dw, float* db, int G, int P,
+                            int C, int act, int fixed_stats, void* dx_half, hipStream_t stream) {
   if (!dy || !x || !mean || !rstd || !workspace || !s1 || !s2 || !dx) return FSV_ERR_BAD_ARG;
-  if (act != FSV_ACT_NONE && !y) return FSV_ERR_BAD_ARG;
+  if (!fsv_norm_bwd_slope_ok(y, w, b, act)) return FSV_ERR_BAD_ARG;
   if (!fsv_half_side_ok(dx_half, (long long)G * P * C, C)) return FSV_ERR_UNSUPPORTED;
   RedPlan pl = fsv_red_plan(G, P, C);
   const int nchunks = pl.nchunks;
-  RedP rp; rp.a = dy; rp.y = y; rp.x = x; rp.mean = mean; rp.rstd = rstd; rp.part = workspace;
+  RedP rp; rp.a = dy; rp.y = y; rp.x = x; rp.mean = mean; rp.rstd = rstd; rp.w = w; rp.b = b; rp.part = workspace;
   rp.P = P; rp.C = C; rp.act = act; fsv_red_no_tail(rp);
   fsv_launch_red<FSV_RED_BWD>(pl, rp, G, stream);
   FSV_LAUNCH(fsv_norm_bwd_final_kernel, dim3(fsv_cdiv(C, 4)), dim3(256), stream, (const double*)workspace, s1, s2, dw,
              db, G, C, nchunks);
   long long total = (long long)G * P * C;
-  fsv_launch_bwd_apply(dy, y, x, mean, rstd, w, (const float*)s1, (const float*)s2, dx, total, (long long)P * C, C, P, act,
+  fsv_launch_bwd_apply(dy, y, x, mean, rstd, w, b, (const float*)s1, (const float*)s2, dx, total, (long long)P * C, C, P, act,
                        fixed_stats, dx_half, stream);
   return fsv_check_launch();
+}
+
+// dy: upstream gradient w.r.t. the activated output y (y may be null when act == none).  Produces dx and, when
+// dw/db are non-null, the affine parameter gradients.  s1/s2: [G*C] scratch.
+int fsv_norm_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* w,
+                 double* workspace, float* s1, float* s2, float* dx, float* dw, float* db, int G, int P, int C, int act,
+                 int fixed_stats, void* dx_half, hipStream_t stream) {
+  if (act != FSV_ACT_NONE && !y) return FSV_ERR_BAD_ARG;
+  return fsv_norm_bwd_two(dy, y, x, mean, rstd, w, nullptr, workspace, s1, s2, dx, dw, db, G, P, C, act, fixed_stats, dx_half, stream);
 }
 
 int fsv_colsum(const float* x, double* workspace, float* out, int G, int P, int C, int accumulate, hipStream_t stream) {
   if (!x || !workspace || !out) return FSV_ERR_BAD_ARG;
   RedPlan pl = fsv_red_plan(G, P, C);
   const int nchunks = pl.nchunks;
-  RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.part = workspace;
+  RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.w = nullptr; rp.b = nullptr; rp.part = workspace;
   rp.P = P; rp.C = C; rp.act = 0; fsv_red_no_tail(rp);
   fsv_launch_red<FSV_RED_COLSUM>(pl, rp, G, stream);
   FSV_LAUNCH(fsv_colsum_final_kernel, dim3(fsv_cdiv(G * C, 4)), dim3(256), stream, (const double*)workspace, out, G,
@@ -652,7 +724,7 @@ int fsv_norm_stats_fused(const float* x, double* workspace, float* mean, float* 
   // more channel slabs than ticket counters (C > 8192 on a small tensor): the two-launch form has no such limit
   if (pl.nslabs > FSV_RED_COUNTERS)
     return fsv_norm_stats_rep(x, workspace, mean, rstd, G, P, C, eps, run_mean, run_var, momentum, rep, stream);
-  RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.part = workspace;
+  RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.w = nullptr; rp.b = nullptr; rp.part = workspace;
   rp.P = P; rp.C = C; rp.act = 0; fsv_red_no_tail(rp);
   rp.counter = counters; rp.o0 = mean; rp.o1 = rstd; rp.o2 = run_mean; rp.o3 = run_var; rp.eps = eps; rp.momentum = momentum;
   rp.rep = rep;
@@ -660,23 +732,26 @@ int fsv_norm_stats_fused(const float* x, double* workspace, float* mean, float* 
   return fsv_check_launch();
 }
 
+// y == null with LeakyReLU(0.2 / 0.1) or ReLU: the slope comes from the sign of the pre-activation, recomputed from x, mean,
+// rstd, w and b (the bias the forward applied; null exactly when w is) by the forward's own expression - the same bits as with
+// y, two tensor reads fewer.  With y given, b is not read.
 int fsv_norm_bwd_fused(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* w,
-                       double* workspace, float* s1, float* s2, float* dx, float* dw, float* db, int G, int P, int C, int act,
-                       int fixed_stats, int* counters, void* dx_half, hipStream_t stream) {
+                       const float* b, double* workspace, float* s1, float* s2, float* dx, float* dw, float* db, int G, int P,
+                       int C, int act, int fixed_stats, int* counters, void* dx_half, hipStream_t stream) {
   if (!fsv_red_fused(counters, G, P, C))
-    return fsv_norm_bwd(dy, y, x, mean, rstd, w, workspace, s1, s2, dx, dw, db, G, P, C, act, fixed_stats, dx_half, stream);
+    return fsv_norm_bwd_two(dy, y, x, mean, rstd, w, b, workspace, s1, s2, dx, dw, db, G, P, C, act, fixed_stats, dx_half, stream);
   if (!dy || !x || !mean || !rstd || !workspace || !s1 || !s2 || !dx) return FSV_ERR_BAD_ARG;
-  if (act != FSV_ACT_NONE && !y) return FSV_ERR_BAD_ARG;
+  if (!fsv_norm_bwd_slope_ok(y, w, b, act)) return FSV_ERR_BAD_ARG;
   if (!fsv_half_side_ok(dx_half, (long long)G * P * C, C)) return FSV_ERR_UNSUPPORTED;
   RedPlan pl = fsv_red_plan(G, P, C, FSV_RED_FUSED_CHUNKS);
   if (pl.nslabs > FSV_RED_COUNTERS)
-    return fsv_norm_bwd(dy, y, x, mean, rstd, w, workspace, s1, s2, dx, dw, db, G, P, C, act, fixed_stats, dx_half, stream);
-  RedP rp; rp.a = dy; rp.y = y; rp.x = x; rp.mean = mean; rp.rstd = rstd; rp.part = workspace;
+    return fsv_norm_bwd_two(dy, y, x, mean, rstd, w, b, workspace, s1, s2, dx, dw, db, G, P, C, act, fixed_stats, dx_half, stream);
+  RedP rp; rp.a = dy; rp.y = y; rp.x = x; rp.mean = mean; rp.rstd = rstd; rp.w = w; rp.b = b; rp.part = workspace;
   rp.P = P; rp.C = C; rp.act = act; fsv_red_no_tail(rp);
   rp.counter = counters; rp.o0 = s1; rp.o1 = s2; rp.o2 = dw; rp.o3 = db;
   fsv_launch_red<FSV_RED_BWD>(pl, rp, G, stream);
   long long total = (long long)G * P * C;
-  fsv_launch_bwd_apply(dy, y, x, mean, rstd, w, (const float*)s1, (const float*)s2, dx, total, (long long)P * C, C, P, act,
+  fsv_launch_bwd_apply(dy, y, x, mean, rstd, w, b, (const float*)s1, (const float*)s2, dx, total, (long long)P * C, C, P, act,
                        fixed_stats, dx_half, stream);
   return fsv_check_launch();
 }
@@ -687,7 +762,7 @@ int fsv_colsum_fused(const float* x, double* workspace, float* out, int G, int P
   if (!x || !workspace || !out) return FSV_ERR_BAD_ARG;
   RedPlan pl = fsv_red_plan(G, P, C, FSV_RED_FUSED_CHUNKS);
   if (pl.nslabs > FSV_RED_COUNTERS) return fsv_colsum(x, workspace, out, G, P, C, accumulate, stream);
-  RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.part = workspace;
+  RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.w = nullptr; rp.b = nullptr; rp.part = workspace;
   rp.P = P; rp.C = C; rp.act = 0; fsv_red_no_tail(rp);
   rp.counter = counters; rp.o0 = out; rp.accumulate = accumulate;
   fsv_launch_red<FSV_RED_COLSUM>(pl, rp, G, stream);
@@ -733,7 +808,7 @@ extern "C" {
 int fsv_norm_sums(const float* x, double* workspace, double* sums, int P, int C, hipStream_t stream) {
   if (!x || !workspace || !sums || P < 1 || C < 1) return FSV_ERR_BAD_ARG;
   RedPlan pl = fsv_red_plan(1, P, C);
-  RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.part = workspace;
+  RedP rp; rp.a = x; rp.y = nullptr; rp.x = nullptr; rp.mean = nullptr; rp.rstd = nullptr; rp.w = nullptr; rp.b = nullptr; rp.part = workspace;
   rp.P = P; rp.C = C; rp.act = 0; fsv_red_no_tail(rp);
   fsv_launch_red<FSV_RED_STATS64>(pl, rp, 1, stream);
   FSV_LAUNCH(fsv_sums_final_kernel, dim3(fsv_cdiv(C, 4)), dim3(256), stream, (const double*)workspace, sums, C, pl.nchunks);
@@ -755,7 +830,7 @@ int fsv_norm_bwd_sums(const float* dy, const float* y, const float* x, const flo
   if (!dy || !x || !mean || !rstd || !workspace || !sums || P < 1 || C < 1) return FSV_ERR_BAD_ARG;
   if (act != FSV_ACT_NONE && !y) return FSV_ERR_BAD_ARG;
   RedPlan pl = fsv_red_plan(1, P, C);
-  RedP rp; rp.a = dy; rp.y = y; rp.x = x; rp.mean = mean; rp.rstd = rstd; rp.part = workspace;
+  RedP rp; rp.a = dy; rp.y = y; rp.x = x; rp.mean = mean; rp.rstd = rstd; rp.w = nullptr; rp.b = nullptr; rp.part = workspace;
   rp.P = P; rp.C = C; rp.act = act; fsv_red_no_tail(rp);
   fsv_launch_red<FSV_RED_BWD>(pl, rp, 1, stream);
   FSV_LAUNCH(fsv_sums_final_kernel, dim3(fsv_cdiv(C, 4)), dim3(256), stream, (const double*)workspace, sums, C, pl.nchunks);
@@ -770,7 +845,7 @@ int fsv_norm_bwd_apply(const float* dy, const float* y, const float* x, const fl
   if (act != FSV_ACT_NONE && !y) return FSV_ERR_BAD_ARG;
   long long total = (long long)P * C;
   if (!fsv_half_side_ok(dx_half, total, C)) return FSV_ERR_UNSUPPORTED;
-  fsv_launch_bwd_apply(dy, y, x, mean, rstd, w, s1, s2, dx, total, total, C, count, act, 0, dx_half, stream);
+  fsv_launch_bwd_apply(dy, y, x, mean, rstd, w, nullptr, s1, s2, dx, total, total, C, count, act, 0, dx_half, stream);
   return fsv_check_launch();
 }
 

@@ -1256,9 +1256,22 @@ def norm_stats(x, groups, pixels, channels, eps, run_mean=None, run_var=None, mo
     return mean, rstd
 
 
-def bn_backward(dy, y, x, mean, rstd, w, g, p, c, act, fixed_stats, affine, world=1):
-    """dx (and dw, db when affine) of a normalisation whose forward pooled its statistics over `world` replicas"""
+# The one-replica backward of a normalisation + LeakyReLU / ReLU site does not need the activated output: the slope is the sign of
+# the pre-activation, which fsv_norm_bwd_fused recomputes from x by the forward's own expression (bit-equal results, two tensor
+# reads fewer per site).  The flag is the A/B switch of tests/test_norm_bwd_noy_emu.py; False keeps y on every path.
+norm_bwd_from_x = True
+_ACTS_SIGN_FROM_PRE = (ACT_LRELU, _conv.ACT_LRELU01, ACT_RELU)
+
+
+def bn_backward(dy, y, x, mean, rstd, w, g, p, c, act, fixed_stats, affine, world=1, b=None):
+    """dx (and dw, db when affine) of a normalisation whose forward pooled its statistics over `world` replicas.  b: the bias of
+    the forward (with w) - given, or w and b both absent, the one-replica path of a LeakyReLU / ReLU site runs without y (y may
+    then be None: it is only read by the paths that keep it)"""
     dx = torch.empty_like(x)
+    if (norm_bwd_from_x and world == 1 and act in _ACTS_SIGN_FROM_PRE and (w is None) == (b is None)):
+        y = None
+    elif y is None and act != ACT_NONE:
+        raise ValueError("bn_backward: act %d needs y on this path (world %d, bias %s)" % (act, world, "given" if b is not None else "absent"))
     if world > 1 and not fixed_stats:
         import torch.distributed as dist
         ws = _ws(1, p, c, x)
@@ -1279,8 +1292,8 @@ def bn_backward(dy, y, x, mean, rstd, w, g, p, c, act, fixed_stats, affine, worl
     db = torch.empty_like(dw) if affine else None
     ws = _ws(g, p, c, x)
     with _hconv.half_side_output(dx) as side:
-        lib.call("fsv_norm_bwd_fused", lib.ptr(dy), lib.ptr(y), lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(w), lib.ptr(ws),
-                 lib.ptr(s1), lib.ptr(s2), lib.ptr(dx), lib.ptr(dw), lib.ptr(db), g, p, c, act, 1 if fixed_stats else 0,
+        lib.call("fsv_norm_bwd_fused", lib.ptr(dy), lib.ptr(y), lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(w),
+                 lib.ptr(b) if y is None else None, lib.ptr(ws), lib.ptr(s1), lib.ptr(s2), lib.ptr(dx), lib.ptr(dw), lib.ptr(db), g, p, c, act, 1 if fixed_stats else 0,
                  _ticket(x), side.ptr(), lib.stream_ptr())
     return dx, dw, db
 
@@ -1318,7 +1331,10 @@ class _NormActFn(torch.autograd.Function):
         ctx.act, ctx.affine = act, weight is not None
         ctx.batch_stats = bool(training or instance or run_mean is None)
         ctx.world = bn_sync_world(g, instance) if ctx.batch_stats else 1
-        ctx.save_for_backward(x, y, mean, rstd, wd if wd is not None else mean)
+        # y above is always fsv_norm_apply's own output, so where bn_backward takes the slope from the recomputed pre-activation
+        # (one replica, LeakyReLU / ReLU) the bias is kept in its place; w and b are both set or both absent here
+        ctx.from_x = bool(norm_bwd_from_x and ctx.world == 1 and act in _ACTS_SIGN_FROM_PRE and (wd is None) == (bd is None))
+        ctx.save_for_backward(x, (bd if bd is not None else mean) if ctx.from_x else y, mean, rstd, wd if wd is not None else mean)
         return y
 
     @staticmethod
@@ -1326,8 +1342,11 @@ class _NormActFn(torch.autograd.Function):
         x, y, mean, rstd, wd = ctx.saved_tensors
         g, p, c = ctx.dims
         dy = to_nhwc(dy)
+        bd = None
+        if ctx.from_x:
+            y, bd = None, (y if ctx.affine else None)
         dx, dw, db = bn_backward(dy, y, x, mean, rstd, wd if ctx.affine else None, g, p, c, ctx.act, not ctx.batch_stats,
-                                 ctx.affine, ctx.world)
+                                 ctx.affine, ctx.world, b=bd)
         return dx, dw, db, None, None, None, None, None, None, None
 
 

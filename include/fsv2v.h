@@ -393,9 +393,14 @@ int fsv_colsum(const float* x, double* workspace, float* out, int G, int P, int 
  * partials, which only pays while the reduction is launch-bound): the two-launch path above. */
 int fsv_norm_stats_fused(const float* x, double* workspace, float* mean, float* rstd, int G, int P, int C, float eps,
                          float* run_mean, float* run_var, float momentum, int rep, int* counters, fsv_stream_t stream);
+/* fsv_norm_bwd_fused alone also runs WITHOUT y for act = LeakyReLU(0.2), LeakyReLU(0.1), ReLU: y == NULL and b = the bias the
+ * forward applied (NULL exactly when w is NULL).  The slope then comes from the sign of the pre-activation
+ * v = ((x - mean) * rstd) * w + b, recomputed per element by the expression fsv_norm_apply evaluates (y > 0 exactly when v > 0
+ * for these three), so s1, s2, dw, db and dx carry the same bits as with y while both passes skip a tensor read.  With y given,
+ * b is not read; y == NULL with tanh / sigmoid, or with only one of w and b, is FSV_ERR_BAD_ARG. */
 int fsv_norm_bwd_fused(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* w,
-                       double* workspace, float* s1, float* s2, float* dx, float* dw, float* db, int G, int P, int C, int act,
-                       int fixed_stats, int* counters, void* dx_half, fsv_stream_t stream);
+                       const float* b, double* workspace, float* s1, float* s2, float* dx, float* dw, float* db, int G, int P,
+                       int C, int act, int fixed_stats, int* counters, void* dx_half, fsv_stream_t stream);
 int fsv_colsum_fused(const float* x, double* workspace, float* out, int G, int P, int C, int accumulate, int* counters,
                      fsv_stream_t stream);
 /* cross-replica BatchNorm (opt-in; apex.parallel.SyncBatchNorm of the reference's multi-process path, normalization.py:15,33,80):
