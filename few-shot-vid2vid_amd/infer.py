@@ -217,7 +217,7 @@ class KeptReferences:
         self.band = None
 
     def band_buffer(self, numel, device):
-        """the one energy / attention band of a banded attention (networks._attention_bands_nograd): the session's, like the other
+        """the one energy / attention band of a banded attention (networks.AttentionBands.attend): the session's, like the other
         static buffers - allocated by the eager warm-up frame, the same memory on every replay (the plan, and with it the size, is
         fixed by the shapes the graph was captured for; other shapes drop the graph and this buffer together)"""
         if self.band is None or self.band.numel() < numel or self.band.device != device:

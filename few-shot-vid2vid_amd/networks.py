@@ -560,22 +560,59 @@ def attention_band_plan(b, n, hw, h, w):
     return [(s, s + 1, r, min(h, r + rows)) for s in range(b) for r in range(0, h, rows)]
 
 
-class AttentionBands:
-    """what attention_module hands out as `atn` in banded mode instead of the attention tensor: the per-reference masses
-    mass[b, h, w, n] (the sum of the attention over each reference's hw key positions: atn_vis and ref_idx), the bands' attention
-    tensors where they live on anyway (with autograd: saved for backward), the second feature map's result when it was taken from the
-    same band loop, and the small operands a later call needs to run the bands again (no_grad, second map not announced)."""
+def _switch01(name):
+    """the 0 / 1 environment switch `name` (default 0; read per call)"""
+    v = os.environ.get(name, '')
+    if not v:
+        return False
+    try:
+        f = float(v)
+    except ValueError:
+        f = -1.0
+    if f not in (0.0, 1.0):
+        raise ValueError("%s=%r: 0 or 1 expected" % (name, v))
+    return f == 1.0
 
-    def __init__(self, plan, b, n, hw, h, w):
-        self.plan, self.b, self.n, self.hw, self.h, self.w = plan, b, n, hw, h, w
-        self.mass = None
-        self.bands = None            # [attention of band i] (autograd mode)
-        self.second = None           # (the tensor it was computed for, its attended feature)
-        self.query = self.kmat = None
 
-    @property
-    def shape(self):
-        return (self.b, self.n * self.hw, self.h, self.w)
+def attention_fused_switch(net=None):
+    """FSV_ATTN_FUSED (0 / 1, default 0; read per call), or a network an InferenceSession(fused_attention=True) marked: the attention
+    of n_shot > 1 as one streaming launch - where autograd is off and ops.attention_fused serves the shape; ignored otherwise"""
+    marked = net is not None and net.__dict__.get('_attn_fused', False)
+    return not torch.is_grad_enabled() and (marked or _switch01('FSV_ATTN_FUSED'))
+
+
+def attention_fused_grad_switch():
+    """FSV_ATTN_FUSED_GRAD (0 / 1, default 0; read per call): the attention of n_shot > 1 of a DIFFERENTIABLE pass as the streaming
+    forward launch plus the streaming backward kernels (ops.attention_fused_grad) - where autograd is on and the backward serves the
+    shape; ignored otherwise.  Independent of FSV_ATTN_FUSED, which speaks for the no-grad passes only."""
+    return torch.is_grad_enabled() and _switch01('FSV_ATTN_FUSED_GRAD')
+
+
+def _kmat(key, b, n, hw):
+    """key features [b*n, c, h, w] as the per-sample 1x1 weights [b, n*hw, c, 1, 1] of the energy GEMM"""
+    c = key.shape[1]
+    return key.reshape(b, n, c, hw).permute(0, 1, 3, 2).reshape(b, n * hw, c, 1, 1)
+
+
+def _xmat(x, b, n, hw):
+    """reference features [b*n, c, h, w] as the per-sample 1x1 weights [b, c, n*hw, 1, 1] of the weighted-sum GEMM (a session's kept
+    operand is in that arrangement already)"""
+    c = x.shape[1]
+    return x if x.dim() == 5 else x.reshape(b, n, c, hw).permute(0, 2, 1, 3).reshape(b, c, n * hw, 1, 1)
+
+
+class _Attention:
+    """the attention of one pass, one of the three kinds below.  attend(values, want_mass) -> [attended map per value map] is the only
+    place a kind's launches are issued: want_mass on the pass's first call, which forms the attention and mass[b, h, w, n] (the sum
+    over each reference's hw key positions: atn_vis, ref_idx); a later call, for a map the first was not told of, re-uses what the
+    kind kept.  operands(): the (name, tensor) pairs of the last call, for a session's sink (infer.KeptReferences.keep).  second:
+    (the tensor, its attended feature) of a map that was announced and rode in the first call.  handle(): what is handed out as `atn`."""
+    KEY, VALUE = 'kmat', 'xmat%d'
+
+    def __init__(self, b, n, hw, h, w):
+        self.b, self.n, self.hw, self.h, self.w = b, n, hw, h, w
+        self.mass = self.second = None
+        self._offer = []
 
     def atn_vis(self):
         return self.mass.permute(0, 3, 1, 2)[-1:, 0:1]
@@ -583,100 +620,144 @@ class AttentionBands:
     def ref_idx(self):
         return torch.argmax(self.mass.sum((1, 2)), dim=1)
 
+    def operands(self):
+        return self._offer
 
-class AttentionFused(AttentionBands):
-    """the `atn` of the streaming attention (ops.attention_fused, FSV_ATTN_FUSED / an InferenceSession's fused_attention): no band
-    plan and no attention tensor at all - the masses of the one launch, the second feature map's result when it was announced, and
-    the query / key features a later call for an unannounced map walks again"""
+    def handle(self):
+        return self
 
-    def __init__(self, b, n, hw, h, w):
-        AttentionBands.__init__(self, None, b, n, hw, h, w)
-        self.key = None
-        self.grad = False            # taken by the differentiable form (ops.attention_fused_grad)
-
-
-def attention_fused_switch(net=None):
-    """FSV_ATTN_FUSED (0 / 1, default 0; read per call), or a network an InferenceSession(fused_attention=True) marked: the attention
-    of n_shot > 1 as one streaming launch - where autograd is off and ops.attention_fused serves the shape; ignored otherwise"""
-    if torch.is_grad_enabled():
-        return False
-    if net is not None and net.__dict__.get('_attn_fused', False):
-        return True
-    v = os.environ.get('FSV_ATTN_FUSED', '')
-    if not v:
-        return False
-    try:
-        f = float(v)
-    except ValueError:
-        f = -1.0
-    if f not in (0.0, 1.0):
-        raise ValueError("FSV_ATTN_FUSED=%r: 0 or 1 expected" % v)
-    return f == 1.0
+    def _offers(self, first, key, values):
+        """the first call offers the key side and its maps as 0, 1; a later call its one map as 1"""
+        self._offer = ([(self.KEY, key)] if first else []) + [(self.VALUE % (i if first else 1), v) for i, v in enumerate(values)]
 
 
-def attention_fused_grad_switch():
-    """FSV_ATTN_FUSED_GRAD (0 / 1, default 0; read per call): the attention of n_shot > 1 of a DIFFERENTIABLE pass as the streaming
-    forward launch plus the streaming backward kernels (ops.attention_fused_grad) - where autograd is on and the backward serves the
-    shape; ignored otherwise.  Independent of FSV_ATTN_FUSED, which speaks for the no-grad passes only."""
-    if not torch.is_grad_enabled():
-        return False
-    v = os.environ.get('FSV_ATTN_FUSED_GRAD', '')
-    if not v:
-        return False
-    try:
-        f = float(v)
-    except ValueError:
-        f = -1.0
-    if f not in (0.0, 1.0):
-        raise ValueError("FSV_ATTN_FUSED_GRAD=%r: 0 or 1 expected" % v)
-    return f == 1.0
+class AttentionDense(_Attention):
+    """the attention tensor [b, n*hw, h, w] in one launch each of energy GEMM, softmax and - per map - weighted sums; attention_module
+    hands out the TENSOR and wraps it again when it comes back (tensor=).  Two flavours, whose bits differ by the order of one fp32
+    sum: the eager pass reduces the tensor for atn_vis / ref_idx, a session's kept frame (mass_from_softmax) takes both from the
+    masses the softmax launch writes (ops.softmax_channels groups)."""
+
+    def __init__(self, b, n, hw, h, w, query=None, kmat=None, tensor=None, mass_from_softmax=False):
+        _Attention.__init__(self, b, n, hw, h, w)
+        self.query, self.kmat, self.tensor, self.mass_from_softmax = query, kmat, tensor, mass_from_softmax
+
+    def handle(self):
+        return self.tensor
+
+    def attend(self, values, want_mass=True):
+        if want_mass:
+            energy_t = ops.batch_conv(self.query, self.kmat, allow_half=False)                   # [b, n*hw, h, w]
+            if self.mass_from_softmax:
+                self.tensor, self.mass = ops.softmax_channels(energy_t, groups=self.n)
+            else:
+                self.tensor = ops.softmax_channels(energy_t)
+        xmats = [_xmat(v, self.b, self.n, self.hw) for v in values]
+        self._offers(want_mass, self.kmat, xmats)
+        return [ops.batch_conv(self.tensor, xm, allow_half=False) for xm in xmats]              # [b, c, h, w]
+
+    def atn_vis(self):
+        if self.mass is not None:
+            return _Attention.atn_vis(self)
+        return self.tensor.reshape(self.b, self.n, self.hw, self.h, self.w).sum(2)[-1:, 0:1]
+
+    def ref_idx(self):
+        if self.mass is not None:
+            return _Attention.ref_idx(self)
+        return torch.argmax(self.tensor.reshape(self.b, self.n, -1).sum(2), dim=1)
 
 
-def _xmat(x, b, n, hw):
-    """reference features [b*n, c, h, w] as the per-sample 1x1 weights [b, c, n*hw, 1, 1] of the weighted-sum GEMM"""
-    c = x.shape[1]
-    return x.reshape(b, n, c, hw).permute(0, 2, 1, 3).reshape(b, c, n * hw, 1, 1)
+def _attention_state(atn, n):
+    """the state behind what attention_module handed out as `atn` (the dense kind hands out its attention tensor)"""
+    if not torch.is_tensor(atn):
+        return atn
+    b, nhw, h, w = atn.shape
+    return AttentionDense(b, n, nhw // n, h, w, tensor=atn)
 
 
-def _attention_bands_nograd(query, kmat, xmats, atn, band_buffer=None):
-    """the band loop without autograd: ONE band of energy lives at a time - the softmax runs in place - in a buffer reused across
-    the bands; the masses come out of the softmax launch.  -> [attended feature per xmat], atn.mass filled"""
-    b, n, hw, h, w = atn.b, atn.n, atn.hw, atn.h, atn.w
-    query = to_nhwc(query.detach())
-    kop = ops.batch_conv_operand(kmat)
-    xops = [ops.batch_conv_operand(xm) for xm in xmats]
-    outs = [empty_nhwc(b, xm.shape[1], h, w, query) for xm in xmats]
-    mass = torch.empty((b, h, w, n), dtype=torch.float32, device=query.device)
-    need = max((s1 - s0) * (r1 - r0) for s0, s1, r0, r1 in atn.plan) * w * n * hw
-    buf = band_buffer(need, query.device) if band_buffer is not None else torch.empty(need, dtype=torch.float32, device=query.device)
-    for s0, s1, r0, r1 in atn.plan:
-        s, rows = s1 - s0, r1 - r0
-        e = buf[:s * rows * w * n * hw].view(s, rows, w, n * hw).permute(0, 3, 1, 2)
-        ops.batch_conv_band(query[s0:s1, :, r0:r1], kop, s0, out=e)
-        ops.softmax_channels(e, groups=n, out=e, mass=mass[s0:s1, r0:r1])
-        for o, xop in zip(outs, xops):
-            ops.batch_conv_band(e, xop, s0, out=o[s0:s1, :, r0:r1])
-    atn.mass = mass
-    return outs
+class AttentionBands(_Attention):
+    """the attention in query bands (attention_band_plan): the dense kind's three launches per band, on the same values, against
+    kmat / xmat operands prepared once.  Without autograd ONE band of energy lives at a time - the softmax runs in place - in a
+    buffer reused across the bands (band_buffer(numel, device): a session's static one), the masses come out of the softmax launch
+    and a later call runs the bands again.  With autograd every band is the differentiable chain of the dense kind on a slice of
+    the query: its attention is saved for backward, so the bands stay alive (`bands`) and a later call re-uses them."""
+
+    def __init__(self, plan, b, n, hw, h, w, query=None, kmat=None, band_buffer=None):
+        _Attention.__init__(self, b, n, hw, h, w)
+        self.plan, self.query, self.kmat, self.band_buffer = plan, query, kmat, band_buffer
+        self.bands = None            # [attention of band i] (autograd mode)
+
+    def attend(self, values, want_mass=True):
+        xmats = [_xmat(v, self.b, self.n, self.hw) for v in values]
+        self._offers(want_mass, self.kmat, xmats)
+        if self.bands is not None or (want_mass and torch.is_grad_enabled()):
+            return self._attend_grad(xmats)
+        if torch.is_grad_enabled():
+            raise RuntimeError("banded attention: the attention of this pass was not kept for a second feature map")
+        return self._attend_nograd(xmats)
+
+    def _attend_nograd(self, xmats):
+        b, n, hw, h, w = self.b, self.n, self.hw, self.h, self.w
+        query = to_nhwc(self.query.detach())
+        kop = ops.batch_conv_operand(self.kmat)
+        xops = [ops.batch_conv_operand(xm) for xm in xmats]
+        outs = [empty_nhwc(b, xm.shape[1], h, w, query) for xm in xmats]
+        mass = torch.empty((b, h, w, n), dtype=torch.float32, device=query.device)
+        need = max((s1 - s0) * (r1 - r0) for s0, s1, r0, r1 in self.plan) * w * n * hw
+        buf = (self.band_buffer(need, query.device) if self.band_buffer is not None
+               else torch.empty(need, dtype=torch.float32, device=query.device))
+        for s0, s1, r0, r1 in self.plan:
+            s, rows = s1 - s0, r1 - r0
+            e = buf[:s * rows * w * n * hw].view(s, rows, w, n * hw).permute(0, 3, 1, 2)
+            ops.batch_conv_band(query[s0:s1, :, r0:r1], kop, s0, out=e)
+            ops.softmax_channels(e, groups=n, out=e, mass=mass[s0:s1, r0:r1])
+            for o, xop in zip(outs, xops):
+                ops.batch_conv_band(e, xop, s0, out=o[s0:s1, :, r0:r1])
+        self.mass = mass
+        return outs
+
+    def _attend_grad(self, xmats):
+        """the masses are detached reductions of each band; the outputs are assembled by ONE concatenation of [pixels, c] pieces - the
+        bands are consecutive pieces of channels-last memory"""
+        b, n, hw, h, w = self.b, self.n, self.hw, self.h, self.w
+        first = self.bands is None
+        bands, pieces, masses = [] if first else self.bands, [[] for _ in xmats], []
+        for i, (s0, s1, r0, r1) in enumerate(self.plan):
+            s, rows = s1 - s0, r1 - r0
+            if first:
+                bands.append(ops.softmax_channels(ops.batch_conv(self.query[s0:s1, :, r0:r1], self.kmat[s0:s1], allow_half=False)))
+                masses.append(bands[i].detach().reshape(s, n, hw, rows * w).sum(2).permute(0, 2, 1).reshape(s * rows * w, n))
+            for p, xm in zip(pieces, xmats):
+                o = ops.batch_conv(bands[i], xm[s0:s1], allow_half=False)
+                p.append(o.permute(0, 2, 3, 1).reshape(s * rows * w, o.shape[1]))
+        if first:
+            self.bands, self.mass = bands, torch.cat(masses, 0).view(b, h, w, n)
+        return [torch.cat(p, 0).view(b, h, w, -1).permute(0, 3, 1, 2) for p in pieces]
 
 
-def _attention_bands_grad(query, kmat, xmats, atn):
-    """the band loop with autograd: every band is the differentiable chain of the unbanded code on a slice of the query (its
-    attention is saved for backward, so the bands stay alive: atn.bands); the masses are detached reductions of each band; the
-    outputs are assembled by ONE concatenation of [pixels, c] pieces - the bands are consecutive pieces of channels-last memory"""
-    b, n, hw, h, w = atn.b, atn.n, atn.hw, atn.h, atn.w
-    bands, pieces, masses = [], [[] for _ in xmats], []
-    for s0, s1, r0, r1 in atn.plan:
-        s, rows = s1 - s0, r1 - r0
-        a = ops.softmax_channels(ops.batch_conv(query[s0:s1, :, r0:r1], kmat[s0:s1], allow_half=False))
-        bands.append(a)
-        masses.append(a.detach().reshape(s, n, hw, rows * w).sum(2).permute(0, 2, 1).reshape(s * rows * w, n))
-        for p, xm in zip(pieces, xmats):
-            o = ops.batch_conv(a, xm[s0:s1], allow_half=False)
-            p.append(o.permute(0, 2, 3, 1).reshape(s * rows * w, o.shape[1]))
-    atn.bands = bands
-    atn.mass = torch.cat(masses, 0).view(b, h, w, n)
-    return [torch.cat(p, 0).view(b, h, w, -1).permute(0, 3, 1, 2) for p in pieces]
+class AttentionFused(_Attention):
+    """the streaming attention (ops.attention_fused; grad: its differentiable form ops.attention_fused_grad) on the encoders' outputs as
+    they lie in memory: ONE launch for the one or two maps of a call, no kmat / xmat arrangement, no band plan, no energy or attention
+    tensor.  A later call walks the same query / key again; in the differentiable pass autograd adds the two contributions to them."""
+    KEY, VALUE = 'key', 'val%d'
+
+    def __init__(self, b, n, hw, h, w, query=None, key=None, grad=False):
+        _Attention.__init__(self, b, n, hw, h, w)
+        self.query, self.key, self.grad = query, key, grad
+
+    def attend(self, values, want_mass=True):
+        op = ops.attention_fused
+        if self.grad and torch.is_grad_enabled():
+            if not want_mass and not ops.attention_fused_grad_supported(self.query, self.key, values, self.n):
+                raise RuntimeError("fused attention: the backward kernels do not serve a second feature map of %d channels: "
+                                   "announce it before the first call" % values[0].shape[1])
+            op = ops.attention_fused_grad
+        elif not want_mass and torch.is_grad_enabled():
+            raise RuntimeError("fused attention: the attention of this pass was not kept for a second feature map")
+        outs, mass = op(self.query, self.key, values, self.n, want_mass=want_mass)
+        if want_mass:
+            self.mass = mass
+        self._offers(want_mass, self.key, values)
+        return outs
 
 
 class FewShotGenerator(nn.Module):
@@ -927,142 +1008,68 @@ class FewShotGenerator(nn.Module):
         """generator.py:298-316.  energy = key^T query over all N*HW reference positions, softmax over them, then the
         attention-weighted sum of the N reference feature maps.  Both batched matrix products run on the gather-GEMM
         kernel as per-sample 1x1 convolutions over the h x w query positions, kept in the transposed arrangement
-        attention_t[b, (n, p_key), y, x] so that the softmax is the channel softmax kernel."""
-        bn, c, h, w = x.shape
+        attention_t[b, (n, p_key), y, x] so that the softmax is the channel softmax kernel.
+        The first call of a pass (attention None) chooses the kind that runs - streaming where its switch is set and the kernels serve
+        the shape, query bands where attention_band_plan asks for them, else dense - and attends x together with a second feature map
+        reference_encoding announced (self._atn_second: the label features under use_label_ref 'mul'; the dense kind leaves it to
+        its own call).  The later call attention_module(xl, None, None, atn) picks that result up, or attends xl by what was kept."""
         n = self.n_shot
-        b = bn // n
+        b, (c, h, w) = x.shape[0] // n, x.shape[1:]
         hw = h * w
-        # an infer.InferenceSession with keep_references collects the two GEMM operands of the reference side while frame 0 runs
-        # (the tensors this pass builds anyway: nothing more is launched here)
-        sink = getattr(self, '_kept_refs', None) if not torch.is_grad_enabled() else None
-        which = 0 if attention is None else 1
-        if isinstance(attention, AttentionBands):
-            return self._attention_second(x, attention, sink)
-        if attention is None and attention_fused_switch(self):
+        if attention is not None:
+            atn = _attention_state(attention, n)
+            if atn.second is not None and atn.second[0] is x:
+                return atn.second[1], attention, atn.atn_vis()
+            outs = atn.attend([x], want_mass=False)
+        else:
             second = self.__dict__.get('_atn_second', None)
-            if ops.attention_fused_serves(b, n, hw, c, [c] + ([second.shape[1]] if second is not None else [])):
-                return self._attention_fused(x, label, label_ref, AttentionFused(b, n, hw, h, w), sink)
-        if attention is None and attention_fused_grad_switch():
-            second = self.__dict__.get('_atn_second', None)
-            if ops.attention_fused_grad_serves(b, n, hw, c, [c] + ([second.shape[1]] if second is not None else [])):
-                return self._attention_fused(x, label, label_ref, AttentionFused(b, n, hw, h, w), None, grad=True)
-        plan = attention_band_plan(b, n, hw, h, w) if attention is None else None
-        if plan is not None:
-            return self._attention_banded(x, label, label_ref, AttentionBands(plan, b, n, hw, h, w), sink)
-        if attention is None:
+            cvs = [c] + ([second.shape[1]] if second is not None else [])
+            fused = attention_fused_switch(self) and ops.attention_fused_serves(b, n, hw, c, cvs)
+            grad = not fused and attention_fused_grad_switch() and ops.attention_fused_grad_serves(b, n, hw, c, cvs)
+            plan = None if fused or grad else attention_band_plan(b, n, hw, h, w)
             key = self.attention_encode(label_ref, 'atn_key')            # [b*n, c, h, w]
             query = self.attention_encode(label, 'atn_query')            # [b, c, h, w]
-            kmat = key.reshape(b, n, c, hw).permute(0, 1, 3, 2).reshape(b, n * hw, c, 1, 1)
-            energy_t = ops.batch_conv(query, kmat, allow_half=False)                        # [b, n*hw, h, w]
-            attention = ops.softmax_channels(energy_t)
-            if sink is not None:
-                sink.collect('kmat', kmat)
-        xmat = x.reshape(b, n, c, hw).permute(0, 2, 1, 3).reshape(b, c, n * hw, 1, 1)
+            if fused or grad:
+                atn = AttentionFused(b, n, hw, h, w, query, key, grad)
+            elif plan is not None:
+                atn = AttentionBands(plan, b, n, hw, h, w, query, _kmat(key, b, n, hw))
+            else:
+                atn, second = AttentionDense(b, n, hw, h, w, query, _kmat(key, b, n, hw)), None
+            if second is not None:
+                self.__dict__.pop('_atn_second')
+            outs = atn.attend([x] + ([second] if second is not None else []))
+            if second is not None:
+                atn.second = (second, outs[1])
+        # an infer.InferenceSession with keep_references collects the operands of the reference side while frame 0 runs (the tensors
+        # this pass builds anyway: nothing more is launched here)
+        sink = getattr(self, '_kept_refs', None) if not torch.is_grad_enabled() else None
         if sink is not None:
-            sink.collect('xmat%d' % which, xmat)
-        out = ops.batch_conv(attention, xmat, allow_half=False)                             # [b, c, h, w]
-        atn_vis = attention.reshape(b, n, hw, h, w).sum(2)[-1:, 0:1]
-        return out, attention, atn_vis
-
-    def _attention_banded(self, x, label, label_ref, atn, sink):
-        """attention_module in query bands (attention_band_plan): the same three launches per band, on the same values, against
-        kmat / xmat operands prepared once.  A second feature map announced by reference_encoding (self._atn_second: the label
-        features under use_label_ref 'mul') is attended in the same loop, while the band exists; the later call
-        attention_module(xl, None, None, atn) then only picks its result up."""
-        b, n, hw = atn.b, atn.n, atn.hw
-        second = self.__dict__.pop('_atn_second', None)
-        key = self.attention_encode(label_ref, 'atn_key')            # [b*n, c, h, w]
-        query = self.attention_encode(label, 'atn_query')            # [b, c, h, w]
-        kmat = key.reshape(b, n, key.shape[1], hw).permute(0, 1, 3, 2).reshape(b, n * hw, key.shape[1], 1, 1)
-        xs = [x] + ([second] if second is not None else [])
-        xmats = [_xmat(t, b, n, hw) for t in xs]
-        if sink is not None:
-            sink.collect('kmat', kmat)
-            for i, xm in enumerate(xmats):
-                sink.collect('xmat%d' % i, xm)
-        if torch.is_grad_enabled():
-            outs = _attention_bands_grad(query, kmat, xmats, atn)
-        else:
-            outs = _attention_bands_nograd(query, kmat, xmats, atn)
-            atn.query, atn.kmat = query, kmat
-        if second is not None:
-            atn.second = (second, outs[1])
-        return outs[0], atn, atn.atn_vis()
-
-    def _attention_fused(self, x, label, label_ref, atn, sink, grad=False):
-        """attention_module as ONE streaming launch (ops.attention_fused) on the encoders' outputs as they lie in memory: no kmat /
-        xmat arrangement, no energy or attention tensor.  An announced second feature map (self._atn_second) rides in the same
-        launch.  grad: the differentiable pass (FSV_ATTN_FUSED_GRAD) - ops.attention_fused_grad, whose backward streams as well."""
-        second = self.__dict__.pop('_atn_second', None)
-        key = self.attention_encode(label_ref, 'atn_key')            # [b*n, c, h, w]
-        query = self.attention_encode(label, 'atn_query')            # [b, c, h, w]
-        vals = [x] + ([second] if second is not None else [])
-        outs, atn.mass = (ops.attention_fused_grad if grad else ops.attention_fused)(query, key, vals, atn.n)
-        atn.query, atn.key, atn.grad = query, key, grad
-        if second is not None:
-            atn.second = (second, outs[1])
-        if sink is not None:
-            sink.collect('key', key)
-            for i, t in enumerate(vals):
-                sink.collect('val%d' % i, t)
-        return outs[0], atn, atn.atn_vis()
-
-    def _attention_second(self, x, atn, sink):
-        """attention_module(x, None, None, atn) with the banded attention `atn`: the result taken in the first call's band loop, or
-        (a caller that did not announce the map) the bands once more"""
-        if atn.second is not None and atn.second[0] is x:
-            return atn.second[1], atn, atn.atn_vis()
-        if isinstance(atn, AttentionFused):        # not announced: a second launch over the same query / key features
-            if atn.grad and atn.query is not None and torch.is_grad_enabled():
-                # the differentiable pass: a second call over the same query / key, autograd adds the two contributions to them
-                if ops.attention_fused_grad_supported(atn.query, atn.key, [x], atn.n):
-                    return ops.attention_fused_grad(atn.query, atn.key, [x], atn.n, want_mass=False)[0][0], atn, atn.atn_vis()
-                raise RuntimeError("fused attention: the backward kernels do not serve a second feature map of %d channels: "
-                                   "announce it before the first call" % x.shape[1])
-            if atn.query is None or torch.is_grad_enabled():
-                raise RuntimeError("fused attention: the attention of this pass was not kept for a second feature map")
-            if sink is not None:
-                sink.collect('val1', x)
-            return ops.attention_fused(atn.query, atn.key, [x], atn.n, want_mass=False)[0][0], atn, atn.atn_vis()
-        xmat = _xmat(x, atn.b, atn.n, atn.hw)
-        if sink is not None:
-            sink.collect('xmat1', xmat)
-        if atn.bands is not None:
-            pieces = []
-            for (s0, s1, r0, r1), a in zip(atn.plan, atn.bands):
-                o = ops.batch_conv(a, xmat[s0:s1], allow_half=False)
-                pieces.append(o.permute(0, 2, 3, 1).reshape(-1, o.shape[1]))
-            out = torch.cat(pieces, 0).view(atn.b, atn.h, atn.w, -1).permute(0, 3, 1, 2)
-        elif atn.query is not None and not torch.is_grad_enabled():
-            out = _attention_bands_nograd(atn.query, atn.kmat, [xmat], atn)[0]
-        else:
-            raise RuntimeError("banded attention: the attention of this pass was not kept for a second feature map")
-        return out, atn, atn.atn_vis()
+            for name, t in atn.operands():
+                sink.collect(name, t)
+        return outs[0], atn.handle(), atn.atn_vis()
 
     def attention_module_kept(self, kept, label):
-        """attention_module on the operands an infer.InferenceSession kept from frame 0 (`keep_references`): kept.kmat is the key
-        encoding of the reference labels and kept.xmats the reference features that enter the attention (image encoder, then label
-        encoder), each in the arrangement its GEMM reads.  Per frame: the query encoder, the energy GEMM, the softmax and the
-        weighted sums - the same launches on the same values as attention_module, so the same bits.  The mass each reference
-        receives comes out of the softmax launch (ops.softmax_channels groups): the attention tensor is not read again.
+        """attention_module on the operands an infer.InferenceSession kept from frame 0 (`keep_references`): after a streaming frame 0
+        kept.key / kept.vals, the key and reference features in their own NHWC memory; otherwise kept.kmat, the key encoding of the
+        reference labels, and kept.xmats, the reference features that enter the attention (image encoder, then label encoder), each in
+        the arrangement its GEMM reads - in query bands where the plan asks for them, the band buffer the session's own (static under a
+        captured graph).  Per frame: the query encoder and the kind's launches, the same launches on the same values as
+        attention_module, so the same bits; the masses come out of the softmax launch, the attention tensor is not read again.
         Returns ([attended image feature, attended label feature or None], atn_vis, ref_idx)."""
         query = self.attention_encode(label, 'atn_query')
-        if kept.key is not None:         # kept by a fused frame 0: the key / reference features in their own NHWC memory
-            outs, mass = ops.attention_fused(query, kept.key, kept.vals, self.n_shot)
-            return outs + [None] * (2 - len(outs)), mass.permute(0, 3, 1, 2)[-1:, 0:1], torch.argmax(mass.sum((1, 2)), dim=1)
-        b, nhw = kept.kmat.shape[:2]
-        h, w = query.shape[2:]
-        plan = attention_band_plan(b, self.n_shot, nhw // self.n_shot, h, w)
-        if plan is not None:             # in query bands, the band buffer the session's own (static under a captured graph)
-            atn = AttentionBands(plan, b, self.n_shot, nhw // self.n_shot, h, w)
-            outs = _attention_bands_nograd(query, kept.kmat, kept.xmats, atn, kept.band_buffer)
-            return outs + [None] * (2 - len(outs)), atn.atn_vis(), atn.ref_idx()
-        energy_t = ops.batch_conv(query, kept.kmat, allow_half=False)
-        attention, mass = ops.softmax_channels(energy_t, groups=self.n_shot)           # mass [b, h, w, n]
-        outs = [ops.batch_conv(attention, xm, allow_half=False) for xm in kept.xmats]
-        atn_vis = mass.permute(0, 3, 1, 2)[-1:, 0:1]
-        ref_idx = torch.argmax(mass.sum((1, 2)), dim=1)
-        return outs + [None] * (2 - len(outs)), atn_vis, ref_idx
+        n = self.n_shot
+        b, (h, w) = query.shape[0], query.shape[2:]
+        hw = h * w
+        if kept.key is not None:
+            atn, values = AttentionFused(b, n, hw, h, w, query, kept.key), kept.vals
+        else:
+            plan, values = attention_band_plan(b, n, hw, h, w), kept.xmats
+            if plan is not None:
+                atn = AttentionBands(plan, b, n, hw, h, w, query, kept.kmat, kept.band_buffer)
+            else:
+                atn = AttentionDense(b, n, hw, h, w, query, kept.kmat, mass_from_softmax=True)
+        outs = atn.attend(values)
+        return outs + [None] * (2 - len(outs)), atn.atn_vis(), atn.ref_idx()
 
     def reference_encoding(self, img_ref, label_ref, encode=True, label=None):
         n = self.n_downsample_G
@@ -1098,10 +1105,7 @@ class FewShotGenerator(nn.Module):
                     self.__dict__.pop('_atn_second', None)
                 if not concat:
                     xl, _, _ = self.attention_module(xl, None, None, atn)
-                if isinstance(atn, AttentionBands):
-                    ref_idx = atn.ref_idx()
-                else:
-                    ref_idx = torch.argmax(atn.reshape(label.shape[0], self.n_shot, -1).sum(2), dim=1)
+                ref_idx = _attention_state(atn, self.n_shot).ref_idx()
         self._atn = (atn_vis, ref_idx)
         if not encode:           # generator.py:370: test-time frames after the first re-use the cached weights
             return x, None

@@ -1044,34 +1044,99 @@ def batch_conv_band(x, operand, s0, out=None):
     return gather_gemm(x.detach(), wt[s0:s0 + s], ldw, cout, x.shape[2], x.shape[3], geom.ty, geom.tx, 1, 1, per_sample=True, out=out)
 
 
-def _attention_fused_plan(b, n, p, c, cvs, want_mass, split):
-    """(nsplit, workspace floats) of fsv_attention_fused_fwd for this shape, or None when the kernel does not serve it"""
-    out = (ctypes.c_longlong * 2)()
-    rc = lib.call_status("fsv_attention_fused_plan", b, n, p, c, cvs[0], cvs[1] if len(cvs) > 1 else 0, 1 if want_mass else 0,
-                         int(split), out)
+def _attention_plan(entry, rc, out):
+    """what a planning entry point of the streaming attention answered: (nsplit, workspace floats), or None when its kernels do not
+    serve the shape (the entry point is named at its own call, where the argument count is checked against the header)"""
     if rc == lib.ENUMS['FSV_ERR_UNSUPPORTED']:
         return None
     if rc != 0:
-        raise lib.FsvError("fsv_attention_fused_plan failed with fsv_status %d" % rc)
+        raise lib.FsvError("%s failed with fsv_status %d" % (entry, rc))
     return int(out[0]), int(out[1])
 
 
+def _attention_fused_plan(b, n, p, c, cvs, want_mass, split):
+    """(nsplit, workspace floats) of fsv_attention_fused_fwd for this shape, or None when the kernel does not serve it"""
+    out = (ctypes.c_longlong * 2)()
+    return _attention_plan("fsv_attention_fused_plan", lib.call_status(
+        "fsv_attention_fused_plan", b, n, p, c, cvs[0], cvs[1] if len(cvs) > 1 else 0, 1 if want_mass else 0, int(split), out), out)
+
+
+def _attention_fused_bwd_plan(b, n, p, c, cvs, split):
+    """(nsplit, workspace floats) of fsv_attention_fused_bwd for this shape, or None when the backward kernels do not serve it"""
+    out = (ctypes.c_longlong * 2)()
+    return _attention_plan("fsv_attention_fused_bwd_plan", lib.call_status(
+        "fsv_attention_fused_bwd_plan", b, n, p, c, cvs[0], cvs[1] if len(cvs) > 1 else 0, int(split), out), out)
+
+
+def _attention_operands(query, key, values, n):
+    """the operands of the streaming attention held to their contract - query [b, c, h, w], key [b n, c, h, w], one or two value maps
+    [b n, cv, h, w], all fp32: -> (b, c, h, w, [cv]), or the reason (a string) they are malformed"""
+    ts = [query, key] + list(values)
+    if not 1 <= len(values) <= 2:
+        return "one or two value maps, got %d" % len(values)
+    if any(t.dim() != 4 or t.dtype != torch.float32 for t in ts):
+        return "4-D fp32 tensors expected, got %s" % [(tuple(t.shape), t.dtype) for t in ts]
+    b, c, h, w = query.shape
+    if n < 1 or tuple(key.shape) != (b * n, c, h, w) or any(tuple(v.shape[0:1] + v.shape[2:]) != (b * n, h, w) for v in values):
+        return ("query %s, key %s, values %s do not belong to %d references"
+                % (tuple(query.shape), tuple(key.shape), [tuple(v.shape) for v in values], n))
+    return b, c, h, w, [v.shape[1] for v in values]
+
+
 def attention_fused_serves(b, n, p, c, cvs):
-    """the same question from the sizes alone: b samples, n references, p = h w positions, c key / query channels, cvs the channel
+    """whether attention_fused serves these sizes: b samples, n references, p = h w positions, c key / query channels, cvs the channel
     counts of the one or two value maps"""
     return 1 <= len(cvs) <= 2 and min(b, n, p, c) >= 1 and _attention_fused_plan(b, n, p, c, list(cvs), True, 0) is not None
+
+
+def attention_fused_grad_serves(b, n, p, c, cvs):
+    """whether attention_fused_grad serves these sizes (the answer of the backward's plan entry point; the forward serves whatever
+    the backward does)"""
+    return (1 <= len(cvs) <= 2 and min(b, n, p, c) >= 1 and _attention_fused_bwd_plan(b, n, p, c, list(cvs), 0) is not None
+            and _attention_fused_plan(b, n, p, c, list(cvs), True, 0) is not None)
 
 
 def attention_fused_supported(query, key, values, n):
     """whether attention_fused serves these tensors (fp32, one or two value maps, every channel count a multiple of 4 up to 256):
     a caller asks before it chooses the fused path, nothing is launched"""
-    ts = [query, key] + list(values)
-    if not 1 <= len(values) <= 2 or n < 1 or any(t.dim() != 4 or t.dtype != torch.float32 for t in ts):
+    o = _attention_operands(query, key, values, n)
+    if isinstance(o, str):
         return False
+    b, c, h, w, cvs = o
+    return _attention_fused_plan(b, n, h * w, c, cvs, True, 0) is not None
+
+
+def attention_fused_grad_supported(query, key, values, n):
+    """whether attention_fused_grad serves these tensors (fp32, one or two value maps, every channel count a multiple of 4 up to
+    128); nothing is launched"""
+    o = _attention_operands(query, key, values, n)
+    if isinstance(o, str):
+        return False
+    b, c, h, w, cvs = o
+    return attention_fused_grad_serves(b, n, h * w, c, cvs)
+
+
+def _attention_fused_launch(query, key, values, n, plan, want_mass, with_lse):
+    """the forward launch of the streaming attention on dense NHWC operands: allocates the outputs, the masses, the log-sum-exp per
+    query (with_lse: what the backward reads; the entry point that writes it) and the plan's workspace -> (outs, mass, lse)"""
     b, c, h, w = query.shape
-    if tuple(key.shape) != (b * n, c, h, w) or any(tuple(v.shape[0:1] + v.shape[2:]) != (b * n, h, w) for v in values):
-        return False
-    return _attention_fused_plan(b, n, h * w, c, [v.shape[1] for v in values], True, 0) is not None
+    nsplit, floats = plan
+    cvs = [v.shape[1] for v in values] + [0]
+    outs = [empty_nhwc(b, v.shape[1], h, w, query) for v in values]
+    mass = torch.empty((b, h, w, n), dtype=torch.float32, device=query.device) if want_mass else None
+    lse = torch.empty((b, h, w), dtype=torch.float32, device=query.device) if with_lse else None
+    ws = torch.empty(floats, dtype=torch.float32, device=query.device) if floats else None
+    lib.check_device(query, key, mass, lse, ws, *(values + outs))
+    q, k, m, wsp = lib.ptr(query), lib.ptr(key), lib.ptr(mass), lib.ptr(ws)
+    v0, v1 = [lib.ptr(v) for v in values] + [None] * (2 - len(values))
+    o0, o1 = [lib.ptr(o) for o in outs] + [None] * (2 - len(outs))
+    if with_lse:
+        lib.call("fsv_attention_fused_fwd_lse", q, k, v0, v1, o0, o1, m, lib.ptr(lse), b, n, h * w, c, cvs[0], cvs[1], nsplit, wsp,
+                 floats, lib.stream_ptr())
+    else:
+        lib.call("fsv_attention_fused_fwd", q, k, v0, v1, o0, o1, m, b, n, h * w, c, cvs[0], cvs[1], nsplit, wsp, floats,
+                 lib.stream_ptr())
+    return outs, mass, lse
 
 
 def attention_fused(query, key, values, n, want_mass=True, split=0):
@@ -1081,64 +1146,18 @@ def attention_fused(query, key, values, n, want_mass=True, split=0):
     attention matrix is never formed (csrc/attention.hip); the channels-last memory of the encoders' outputs is read where it lies.
     split: the number of key ranges per query tile (0: the library's choice for the shape; a finishing launch combines them).  The
     launch's scratch (fsv_attention_fused_plan) is allocated here, per call; under a captured graph it lives in the graph's pool."""
-    ts = [query, key] + list(values)
-    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in [query, key] + list(values)):
         raise ValueError("attention_fused is forward-only (an input requires grad)")
-    if not 1 <= len(values) <= 2:
-        raise ValueError("attention_fused: one or two value maps, got %d" % len(values))
-    if any(t.dim() != 4 or t.dtype != torch.float32 for t in ts):
-        raise ValueError("attention_fused: 4-D fp32 tensors expected, got %s" % [(tuple(t.shape), t.dtype) for t in ts])
-    query, key = to_nhwc(query.detach()), to_nhwc(key.detach())
-    values = [to_nhwc(v.detach()) for v in values]
-    b, c, h, w = query.shape
-    if tuple(key.shape) != (b * n, c, h, w) or any(tuple(v.shape[0:1] + v.shape[2:]) != (b * n, h, w) for v in values):
-        raise ValueError("attention_fused: query %s, key %s, values %s do not belong to %d references"
-                         % (tuple(query.shape), tuple(key.shape), [tuple(v.shape) for v in values], n))
-    cvs = [v.shape[1] for v in values]
+    o = _attention_operands(query, key, values, n)
+    if isinstance(o, str):
+        raise ValueError("attention_fused: " + o)
+    b, c, h, w, cvs = o
     plan = _attention_fused_plan(b, n, h * w, c, cvs, want_mass, split)
     if plan is None:
         raise lib.FsvError("attention_fused: channels %s are not served (multiples of 4 up to 256): ask attention_fused_supported"
                            % ([c] + cvs))
-    nsplit, floats = plan
-    outs = [empty_nhwc(b, cv, h, w, query) for cv in cvs]
-    mass = torch.empty((b, h, w, n), dtype=torch.float32, device=query.device) if want_mass else None
-    ws = torch.empty(floats, dtype=torch.float32, device=query.device) if floats else None
-    lib.check_device(query, key, mass, ws, *(values + outs))
-    two = len(values) > 1
-    lib.call("fsv_attention_fused_fwd", lib.ptr(query), lib.ptr(key), lib.ptr(values[0]), lib.ptr(values[1]) if two else None,
-             lib.ptr(outs[0]), lib.ptr(outs[1]) if two else None, lib.ptr(mass), b, n, h * w, c, cvs[0], cvs[1] if two else 0,
-             nsplit, lib.ptr(ws), floats, lib.stream_ptr())
-    return outs, mass
-
-
-def _attention_fused_bwd_plan(b, n, p, c, cvs, split):
-    """(nsplit, workspace floats) of fsv_attention_fused_bwd for this shape, or None when the backward kernels do not serve it"""
-    out = (ctypes.c_longlong * 2)()
-    rc = lib.call_status("fsv_attention_fused_bwd_plan", b, n, p, c, cvs[0], cvs[1] if len(cvs) > 1 else 0, int(split), out)
-    if rc == lib.ENUMS['FSV_ERR_UNSUPPORTED']:
-        return None
-    if rc != 0:
-        raise lib.FsvError("fsv_attention_fused_bwd_plan failed with fsv_status %d" % rc)
-    return int(out[0]), int(out[1])
-
-
-def attention_fused_grad_serves(b, n, p, c, cvs):
-    """whether attention_fused_grad serves these sizes (the answer of the backward's plan entry point; the forward serves whatever
-    the backward does): b samples, n references, p = h w positions, c key / query channels, cvs the one or two value maps' channels"""
-    return (1 <= len(cvs) <= 2 and min(b, n, p, c) >= 1 and _attention_fused_bwd_plan(b, n, p, c, list(cvs), 0) is not None
-            and _attention_fused_plan(b, n, p, c, list(cvs), True, 0) is not None)
-
-
-def attention_fused_grad_supported(query, key, values, n):
-    """whether attention_fused_grad serves these tensors (fp32, one or two value maps, every channel count a multiple of 4 up to
-    128); nothing is launched"""
-    ts = [query, key] + list(values)
-    if not 1 <= len(values) <= 2 or n < 1 or any(t.dim() != 4 or t.dtype != torch.float32 for t in ts):
-        return False
-    b, c, h, w = query.shape
-    if tuple(key.shape) != (b * n, c, h, w) or any(tuple(v.shape[0:1] + v.shape[2:]) != (b * n, h, w) for v in values):
-        return False
-    return attention_fused_grad_serves(b, n, h * w, c, [v.shape[1] for v in values])
+    return _attention_fused_launch(to_nhwc(query.detach()), to_nhwc(key.detach()), [to_nhwc(v.detach()) for v in values], n, plan,
+                                   want_mass, False)[:2]
 
 
 class _AttentionFusedFn(torch.autograd.Function):
@@ -1149,17 +1168,8 @@ class _AttentionFusedFn(torch.autograd.Function):
         query, key = to_nhwc(query), to_nhwc(key)
         values = [to_nhwc(v) for v in values]
         b, c, h, w = query.shape
-        cvs = [v.shape[1] for v in values]
-        nsplit, floats = _attention_fused_plan(b, n, h * w, c, cvs, want_mass, split)
-        outs = [empty_nhwc(b, cv, h, w, query) for cv in cvs]
-        mass = torch.empty((b, h, w, n), dtype=torch.float32, device=query.device) if want_mass else None
-        lse = torch.empty((b, h, w), dtype=torch.float32, device=query.device)
-        ws = torch.empty(floats, dtype=torch.float32, device=query.device) if floats else None
-        lib.check_device(query, key, mass, lse, ws, *(values + outs))
-        two = len(values) > 1
-        lib.call("fsv_attention_fused_fwd_lse", lib.ptr(query), lib.ptr(key), lib.ptr(values[0]), lib.ptr(values[1]) if two else None,
-                 lib.ptr(outs[0]), lib.ptr(outs[1]) if two else None, lib.ptr(mass), lib.ptr(lse), b, n, h * w, c, cvs[0],
-                 cvs[1] if two else 0, nsplit, lib.ptr(ws), floats, lib.stream_ptr())
+        plan = _attention_fused_plan(b, n, h * w, c, [v.shape[1] for v in values], want_mass, split)
+        outs, mass, lse = _attention_fused_launch(query, key, values, n, plan, want_mass, True)
         ctx.n, ctx.split, ctx.nv = n, split, len(values)
         ctx.save_for_backward(query, key, lse, *(values + outs))
         if mass is None:
@@ -1198,16 +1208,10 @@ def attention_fused_grad(query, key, values, n, want_mass=True, split=0):
     probabilities from it tile by tile: no [n hw, hw] tensor in either direction, no kmat / xmat arrangement, exact fp32, no atomics.
     Channel counts are multiples of 4 up to 128 (attention_fused_grad_supported).  split: the number of key ranges of the forward
     launch and of the query gradient's launch (0: the library's choice).  The scratch of both calls is allocated per call."""
-    ts = [query, key] + list(values)
-    if not 1 <= len(values) <= 2:
-        raise ValueError("attention_fused_grad: one or two value maps, got %d" % len(values))
-    if any(t.dim() != 4 or t.dtype != torch.float32 for t in ts):
-        raise ValueError("attention_fused_grad: 4-D fp32 tensors expected, got %s" % [(tuple(t.shape), t.dtype) for t in ts])
-    b, c, h, w = query.shape
-    if tuple(key.shape) != (b * n, c, h, w) or any(tuple(v.shape[0:1] + v.shape[2:]) != (b * n, h, w) for v in values):
-        raise ValueError("attention_fused_grad: query %s, key %s, values %s do not belong to %d references"
-                         % (tuple(query.shape), tuple(key.shape), [tuple(v.shape) for v in values], n))
-    cvs = [v.shape[1] for v in values]
+    o = _attention_operands(query, key, values, n)
+    if isinstance(o, str):
+        raise ValueError("attention_fused_grad: " + o)
+    b, c, h, w, cvs = o
     if (_attention_fused_bwd_plan(b, n, h * w, c, cvs, split) is None
             or _attention_fused_plan(b, n, h * w, c, cvs, want_mass, split) is None):
         raise lib.FsvError("attention_fused_grad: channels %s are not served (multiples of 4 up to 128): ask "
