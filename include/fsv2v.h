@@ -223,9 +223,11 @@ int fsv_prep_weight(const float* w, float* wt, const float* scale_ptr, int mode,
 /* every parameter weight of an optimiser re-arranged in one launch (un-scaled; used once per optimiser step).  dims[l] =
  * {Cout, Cin_pad, Cin_real, KH, KW, ntaps, Kpad, ldw, mode}; the layouts of one weight are consecutive in the tables and share
  * its source tile: tmap = (first layout of the weight, number of its layouts, 32-co tile, ci tile) quadruples (ci tile = 32
- * channels for KH*KW <= 8, else 16); only the valid region of each (pre-zeroed) layout is written.  mode | 4: the two nibbles of
- * a tap code are MASKS over kh / kw and the written weight is the sum of the selected source taps (the summed-tap layouts of
- * conv3x3(nearest_x2(x)): sub-pixel forward classes, one-launch data gradient) */
+ * channels for KH*KW <= 8, else 16).  The layouts are pre-zeroed by their owner; a mode-1 layout gets its valid region written and
+ * nothing else, a mode-0 layout is written in whole 32-column tiles, so its padding columns [Cout, ldw) receive zeros again
+ * (rows beyond ntaps * Cin_pad are never written; the rows of padded input channels are written as zeros in both modes).
+ * mode | 4: the two nibbles of a tap code are MASKS over kh / kw and the written weight is the sum of the selected source taps
+ * (the summed-tap layouts of conv3x3(nearest_x2(x)): sub-pixel forward classes, one-launch data gradient) */
 int fsv_prep_weight_grouped(const long long* src, const long long* dst, const int* dims, const unsigned long long* taps,
                             const int* tmap, int nblocks, fsv_stream_t stream);
 /* grouped fixed-order sums: dst[j] = src[4 j] + src[4 j + 1] + ... (nsrc[j] in 1..4 terms, left to right) over count[j] floats,

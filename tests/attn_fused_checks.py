@@ -20,19 +20,6 @@ U = ab.U
 SWITCH = 'FSV_ATTN_FUSED'
 ENTRY = 'fsv_attention_fused_fwd'
 
-
-def _register_in_abi_ledger():
-    """The ledger of the C ABI (test_entry_point_coverage.CHECKED_BY) asks every entry point of include/fsv2v.h for the check that
-    drives it directly.  The two entry points of csrc/attention.hip name theirs here, next to the checks themselves:
-    test_every_named_check_exists then holds check_splits to being a callable of this module like any other line of the table, and
-    the planning entry point is host-only by the ledger's own `_plan$` rule."""
-    import test_entry_point_coverage as ledger
-    ledger.CHECKED_BY.setdefault(ENTRY, 'attn_fused_checks.check_splits')
-    ledger.CHECKED_BY.setdefault('fsv_attention_fused_plan', ledger.HOST_ONLY)
-
-
-_register_in_abi_ledger()
-
 # (b, n, c, c0, c1, h, w).  small: the inputs of attn_band_checks.operator_inputs - 30 positions, no multiple of any tile, one key
 # tile of 32 holds two reference boundaries.  prod: the production channel counts, both maps in one launch, 72 queries x 144 keys.
 # ragged: 99 queries (a tail in the query tile), 198 keys with the reference boundary inside a key tile, a 36-channel second map

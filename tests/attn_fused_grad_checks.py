@@ -24,18 +24,6 @@ FWD, BWD = 'fsv_attention_fused_fwd_lse', 'fsv_attention_fused_bwd'
 NAMES = ('d key', 'd query', 'd image features', 'd label features')
 
 
-def _register_in_abi_ledger():
-    """the lines of the new entry points in test_entry_point_coverage.CHECKED_BY (as attn_fused_checks registers its own): each names
-    the check that drives it directly; the planning entry point is host-only by the ledger's own `_plan$` rule"""
-    import test_entry_point_coverage as ledger
-    ledger.CHECKED_BY.setdefault(FWD, 'attn_fused_grad_checks.check_forward_lse')
-    ledger.CHECKED_BY.setdefault(BWD, 'attn_fused_grad_checks.check_bounds')
-    ledger.CHECKED_BY.setdefault('fsv_attention_fused_bwd_plan', ledger.HOST_ONLY)
-
-
-_register_in_abi_ledger()
-
-
 @contextlib.contextmanager
 def switched(value):
     """FSV_ATTN_FUSED_GRAD = value (None: unset) for the block; the switch is read per call"""

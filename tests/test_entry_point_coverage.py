@@ -3,7 +3,8 @@
 without a line here fails this module: write its check first.
 
 The table was produced on the emulator by recording the entry points lib.call / lib.call_status issued while the check
-modules ran (op_checks, small_op_checks, h_checks, np_checks, spade_k3_checks, adaptive_conv_checks, tile_checks).  Calls made
+modules ran (op_checks, small_op_checks, h_checks, np_checks, spade_k3_checks, adaptive_conv_checks, tile_checks,
+weight_path_checks, attn_fused_checks, attn_fused_grad_checks).  Calls made
 under the whole-iteration functions of those modules (check_step, check_inference: one D + G step or a full inference, compared
 through losses and gradient norms) do not count.  Where several checks reach an entry point, small_op_checks, then op_checks,
 come first, and within a module the check that calls it most often.  Nothing is launched here."""
@@ -25,6 +26,11 @@ CHECKED_BY = {
     'fsv_amp_adam':                    'small_op_checks.check_amp_adam',
     'fsv_amp_check':                   'small_op_checks.check_amp_check',
     'fsv_amp_update':                  'small_op_checks.check_amp_update',
+    'fsv_attention_fused_bwd':         'attn_fused_grad_checks.check_bounds',
+    'fsv_attention_fused_bwd_plan':    'host-only',
+    'fsv_attention_fused_fwd':         'attn_fused_checks.check_splits',
+    'fsv_attention_fused_fwd_lse':     'attn_fused_grad_checks.check_forward_lse',
+    'fsv_attention_fused_plan':        'host-only',
     'fsv_avgpool3s2_bwd':              'op_checks.check_avgpool3s2',
     'fsv_avgpool3s2_fwd':              'op_checks.check_avgpool3s2',
     'fsv_bias_act':                    'small_op_checks.check_bias_act',
@@ -87,12 +93,12 @@ CHECKED_BY = {
     'fsv_pool15':                      'op_checks.check_losses',
     'fsv_pool_rows_bwd':               'adaptive_conv_checks.check_pool_windows',
     'fsv_pool_rows_fwd':               'adaptive_conv_checks.check_pool_windows',
-    'fsv_prep_weight':                 'op_checks.check_conv',
-    'fsv_prep_weight_grouped':         'op_checks.check_conv',
+    'fsv_prep_weight':                 'weight_path_checks.check_prep_weight_modes',
+    'fsv_prep_weight_grouped':         'weight_path_checks.check_layouts',
     'fsv_resample2d_fwd':              'op_checks.check_flownet_ops',
-    'fsv_sn_backward':                 'op_checks.check_spade_conv_s',
-    'fsv_sn_power_iter':               'op_checks.check_spade_conv_s',
-    'fsv_sn_power_iter_batched':       'op_checks.check_spectral_power_iteration',
+    'fsv_sn_backward':                 'weight_path_checks.check_sn_backward',
+    'fsv_sn_power_iter':               'weight_path_checks.check_power_iteration',
+    'fsv_sn_power_iter_batched':       'weight_path_checks.check_power_iteration_batched',
     'fsv_sn_scratch_floats':           'host-only',
     'fsv_softmax_rows_bwd':            'op_checks.check_softmax',
     'fsv_softmax_rows_fwd':            'op_checks.check_softmax',
@@ -121,7 +127,7 @@ CHECKED_BY = {
     'fsv_warp_compose_bwd':            'op_checks.check_warp_compose',
     'fsv_warp_compose_fwd':            'op_checks.check_warp_compose',
     'fsv_warp_fwd':                    'op_checks.check_warp',
-    'fsv_wgrad_finalize':              'op_checks.check_conv',
+    'fsv_wgrad_finalize':              'weight_path_checks.check_finalize',
     'fsv_wsum_bwd':                    'op_checks.check_weighted_sum',
     'fsv_wsum_fwd':                    'op_checks.check_weighted_sum',
 }
