@@ -21,12 +21,9 @@
 // ascending split order - no atomics, the same bits on every run.  The per-reference masses come from the same walk: the sum of a
 // reference's probabilities is kept relative to the running maximum and written, with that maximum, when the walk leaves the
 // reference (a key tile may hold several reference boundaries); the finishing pass rescales it to the final maximum.
-#include "fsv_common.h"
+#include "attention_shared.h"   // FSV_AF_BQ / _BK / _MAX_SPLIT, fsv_af_tile0; fsv_af_plan and fsv_af_finish are defined here
 
-#define FSV_AF_BQ 128          // query positions per workgroup (32 per wave)
-#define FSV_AF_BK 32           // keys per tile
 #define FSV_AF_NV 8            // 32-channel output tiles per launch at most (both value maps together)
-#define FSV_AF_MAX_SPLIT 8
 
 struct AttnFusedP {
   const float* q;              // [B][P][C]
@@ -42,9 +39,6 @@ struct AttnFusedP {
   int cv[2], nv[2];            // channels of the two maps, tiles taken from each (second: 0 when absent)
   int B, N, P, C, ncq, nsplit, ntiles;
 };
-
-// the key tiles [t0, t1) of split s
-__host__ __device__ static inline int fsv_af_tile0(int s, int nsplit, int ntiles) { return (int)((long long)s * ntiles / nsplit); }
 
 // PF: the global loads of tile t + 1 are in flight while tile t is computed (their registers live across the matrix work);
 // the 256-channel form has no registers left for that: it loads a tile right before it stores it and carries NV = 4 output tiles
@@ -292,7 +286,7 @@ __global__ __launch_bounds__(256) void fsv_attn_fused_finish_kernel(AttnFinishP 
   p.mass[row * p.N + g] = sum / l;
 }
 
-static int fsv_af_plan(int B, int N, int P, int C0, int C1, int want_mass, int nsplit, int* split_out, long long* ws_floats) {
+int fsv_af_plan(int B, int N, int P, int C0, int C1, int want_mass, int nsplit, int* split_out, long long* ws_floats) {
   const long long NP = (long long)N * P;
   const int ntiles = (int)((NP + FSV_AF_BK - 1) / FSV_AF_BK);
   if (nsplit <= 0) {            // fill 256 compute units: a function of the shape alone
@@ -311,6 +305,21 @@ static int fsv_af_plan(int B, int N, int P, int C0, int C1, int want_mass, int n
   *split_out = nsplit;
   *ws_floats = ws;
   return FSV_OK;
+}
+
+// the finishing launch and the status of this file's launches since the last check (the half walk of attention_h.hip ends here too)
+int fsv_af_finish(const float* ml, const float* mp, const float* po0, const float* po1, float* o0, float* o1, float* mass, float* lse,
+                  int B, int N, int P, int C0, int C1, int nsplit, hipStream_t stream) {
+  AttnFinishP f;
+  f.ml = ml; f.mp = mp; f.po[0] = po0; f.po[1] = po1; f.o[0] = o0; f.o[1] = o1; f.mass = mass; f.lse = lse;
+  f.cv[0] = C0; f.cv[1] = C1;
+  f.B = B; f.N = N; f.P = P; f.nsplit = nsplit; f.ntiles = (int)(((long long)N * P + FSV_AF_BK - 1) / FSV_AF_BK);
+  f.rows = (long long)B * P;
+  f.nq0 = nsplit > 1 ? C0 / 4 : 0; f.nq1 = nsplit > 1 ? C1 / 4 : 0;
+  f.per_row = f.nq0 + f.nq1 + (mass ? N : 0);
+  const long long items = f.rows * f.per_row;
+  FSV_LAUNCH(fsv_attn_fused_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), stream, f);
+  return fsv_check_launch();
 }
 
 static int fsv_af_shape(const void* v1, int B, int N, int P, int C, int C0, int C1) {
@@ -385,17 +394,7 @@ static int fsv_af_forward(const float* q, const float* k, const float* v0, const
     if (C <= 128) FSV_LAUNCH((fsv_attn_fused_kernel<4, true, FSV_AF_NV>), grid, dim3(256), stream, p);
     else FSV_LAUNCH((fsv_attn_fused_kernel<8, false, 4>), grid, dim3(256), stream, p);
   }
-  if (split > 1 || mass) {
-    AttnFinishP f;
-    f.ml = ml; f.mp = mp; f.po[0] = po0; f.po[1] = po1; f.o[0] = o0; f.o[1] = o1; f.mass = mass; f.lse = lse;
-    f.cv[0] = C0; f.cv[1] = C1;
-    f.B = B; f.N = N; f.P = P; f.nsplit = split; f.ntiles = (int)((NP + FSV_AF_BK - 1) / FSV_AF_BK);
-    f.rows = rows;
-    f.nq0 = split > 1 ? C0 / 4 : 0; f.nq1 = split > 1 ? C1 / 4 : 0;
-    f.per_row = f.nq0 + f.nq1 + (mass ? N : 0);
-    const long long items = rows * f.per_row;
-    FSV_LAUNCH(fsv_attn_fused_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), stream, f);
-  }
+  if (split > 1 || mass) return fsv_af_finish(ml, mp, po0, po1, o0, o1, mass, lse, B, N, P, C0, C1, split, stream);
   return fsv_check_launch();
 }
 

@@ -53,6 +53,14 @@ no kmat / xmat arrangement with its K-major layouts.  Not bit-equal to the eager
 the weighted sums changes (a shape the kernel does not serve runs the launches above).  The mark sits on netG until close()
 (like the kept reference side): model.inference() or another session on the same model is fused too while this one is attached.
 
+fused_attention='half' (n_shot > 1): as above with the attention on the f16 matrix cores (ops.attention_fused_half,
+csrc/attention_h.hip: energies from split half operands - about 22 bits -, plain half probabilities and values, fp32 softmax and
+accumulation) wherever that kernel serves the shape - every channel count a multiple of 8 up to 128 -, the fp32 streaming launch
+elsewhere.  With keep_references the session keeps the PREPARED operands (`KeptReferences.half`: the two half planes of the keys,
+the half key-contiguous value maps - half the memory of the fp32 maps, the same for the keys) and a steady frame issues the query
+encoder, one fsv_attention_fused_fwd_h and the finishing launch: no prep, no cast, no arrangement.  Without keep_references the
+prep launch runs per frame, in the captured graph.
+
 inputs_u8=True: the three inputs arrive as uint8 with the channel last ([B, 1, H, W, C] / [B, N, H, W, C]), as a video pipeline
 delivers them, and are converted on the device into the session's static inputs (ops.image_from_u8: the dataset's ToTensor +
 Normalize(0.5, 0.5), bit-exact).  Class-index label maps (label_nc != 0) are not covered: the flag raises for them.
@@ -213,6 +221,7 @@ class KeptReferences:
     def __init__(self):
         self.ready, self.kmat, self.xmats = False, None, []
         self.key, self.vals = None, []           # a fused frame 0 (ops.attention_fused): the encoders' outputs as they lie in memory
+        self.half = None                         # a half frame 0 (ops.attention_fused_half): ops.AttentionHalfOperands, the session's own
         self._got = None
         self.band = None
 
@@ -236,6 +245,8 @@ class KeptReferences:
 
     def keep(self, frozen):
         got, self._got = self._got, None
+        if got and 'half' in got and 'half_val0' in got:
+            return self._keep_half(got)
         fused = bool(got) and 'key' in got and 'val0' in got
         if not fused and (not got or 'kmat' not in got or 'xmat0' not in got):
             raise RuntimeError("keep_references: frame 0 did not pass through the attention module")
@@ -251,19 +262,38 @@ class KeptReferences:
                 dst.copy_(src)
         elif fused:
             old = [ops.to_nhwc(t.detach()).clone() for t in new]           # (clone keeps the dense NHWC strides)
-            self.key, self.vals, self.kmat, self.xmats, self.band = old[0], old[1:], None, [], None
+            self.key, self.vals, self.kmat, self.xmats, self.band, self.half = old[0], old[1:], None, [], None, None
         else:
             old = [t.detach().clone(memory_format=torch.contiguous_format) for t in new]
-            self.kmat, self.xmats, self.key, self.vals = old[0], old[1:], None, []
+            self.kmat, self.xmats, self.key, self.vals, self.half = old[0], old[1:], None, [], None
         if not fused:                            # (the fused kernel reads the kept tensors themselves: no layout to freeze)
             for t in old:
                 t._fsv_frozen = frozen
         self.ready = True
         return same
 
+    def _keep_half(self, got):
+        """a half frame 0: the prepared operands (half planes of the keys, half key-contiguous value maps - a second map that was
+        not announced came from a later call) into the session's own, rewritten in place for equal shapes; nothing else is kept"""
+        src = got['half']
+        vts = [got['half_val0']] + ([got['half_val1']] if 'half_val1' in got else [])
+        new = [src.kh, src.kl] + vts
+        old = self.half.tensors() if self.half is not None else []
+        same = len(old) == len(new) and all(a.shape == b.shape and a.device == b.device for a, b in zip(old, new))
+        if same:
+            for dst, s in zip(old, new):
+                dst.copy_(s)
+        else:
+            own = [t.detach().clone() for t in new]
+            self.half = ops.AttentionHalfOperands(own[0], own[1], own[2:], src.b, src.n, src.p, src.c, [t.shape[1] for t in vts],
+                                                  src.nps)
+            self.key, self.vals, self.kmat, self.xmats, self.band = None, [], None, [], None
+        self.ready = True
+        return same
+
     def drop(self):
         self.ready, self.kmat, self.xmats, self._got, self.band = False, None, [], None, None
-        self.key, self.vals = None, []
+        self.key, self.vals, self.half = None, [], None
 
 
 class FrameOutputs(tuple):
@@ -320,9 +350,15 @@ class InferenceSession:
         if self._kept is not None:
             netG._kept_refs = self._kept
         # fused_attention: the mark networks.attention_fused_switch reads, on netG for as long as the session is attached
+        # 'half': also the mark networks.attention_half_switch reads - the half kernel where it serves the shape, the fp32 one elsewhere
+        if fused_attention not in (False, True, 'half'):
+            raise ValueError("fused_attention=%r: False, True or 'half' expected" % (fused_attention,))
         self.fused_attention = bool(fused_attention) and netG.n_shot > 1
+        self.half_attention = self.fused_attention and fused_attention == 'half'
         if self.fused_attention:
             netG._attn_fused = True
+        if self.half_attention:
+            netG._attn_half = True
         self._drop_graph()
         self._drop_buffers()
         self._sig = None
@@ -432,6 +468,7 @@ class InferenceSession:
                 del self.model.netG._kept_refs
         if self.fused_attention:
             self.model.netG.__dict__.pop('_attn_fused', None)
+            self.model.netG.__dict__.pop('_attn_half', None)
         self._drop_buffers()
         if getattr(self.model, '_infer_session', None) is self:
             self.model._infer_session = None

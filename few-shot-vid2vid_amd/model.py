@@ -837,6 +837,9 @@ class Vid2VidModel(nn.Module):
         Like the kept reference side, the mark sits on netG until close(): while such a session is attached, inference() on this
         model and any other session on it take the streaming attention too - close() the session first (a session that is dropped
         without close() leaves the mark behind).
+        fused_attention='half': that launch on the f16 matrix cores (ops.attention_fused_half; split-half energies, fp32 softmax)
+        where every attention channel count is a multiple of 8 up to 128, the fp32 launch elsewhere; with keep_references the
+        prepared half operands are kept and a steady frame issues no prep launch.
         keep_references=True (n_shot > 1; a no-op with one reference): the reference side of a sequence - the reference encoders up
         to the attention level and the attention keys - is read at frame 0 and kept until reset() / refreeze().  Unlike
         inference(), which re-reads ref_labels / ref_images on every frame, such a session ignores the references passed on

@@ -581,6 +581,17 @@ def attention_fused_switch(net=None):
     return not torch.is_grad_enabled() and (marked or _switch01('FSV_ATTN_FUSED'))
 
 
+def attention_half_switch(net):
+    """FSV_ATTN_FUSED_HALF (0 / 1, default 0; read per call), or a network an InferenceSession(fused_attention='half') marked: the
+    attention of n_shot > 1 as the streaming launch on the f16 matrix cores (ops.attention_fused_half) - an INFERENCE path: where
+    autograd is off, the generator is in eval() and the kernel serves the shape; ignored otherwise (a training pass never takes it,
+    nor does the D step's generator pass: the generator is in train() there).  Independent of FSV_ATTN_FUSED; where both are set and
+    the half kernel serves the shape, half wins."""
+    if torch.is_grad_enabled() or net.training:
+        return False
+    return bool(net.__dict__.get('_attn_half', False)) or _switch01('FSV_ATTN_FUSED_HALF')
+
+
 def attention_fused_grad_switch():
     """FSV_ATTN_FUSED_GRAD (0 / 1, default 0; read per call): the attention of n_shot > 1 of a DIFFERENTIABLE pass as the streaming
     forward launch plus the streaming backward kernels (ops.attention_fused_grad) - where autograd is on and the backward serves the
@@ -602,7 +613,7 @@ def _xmat(x, b, n, hw):
 
 
 class _Attention:
-    """the attention of one pass, one of the three kinds below.  attend(values, want_mass) -> [attended map per value map] is the only
+    """the attention of one pass, one of the kinds below.  attend(values, want_mass) -> [attended map per value map] is the only
     place a kind's launches are issued: want_mass on the pass's first call, which forms the attention and mass[b, h, w, n] (the sum
     over each reference's hw key positions: atn_vis, ref_idx); a later call, for a map the first was not told of, re-uses what the
     kind kept.  operands(): the (name, tensor) pairs of the last call, for a session's sink (infer.KeptReferences.keep).  second:
@@ -757,6 +768,29 @@ class AttentionFused(_Attention):
         if want_mass:
             self.mass = mass
         self._offers(want_mass, self.key, values)
+        return outs
+
+
+class AttentionFusedHalf(_Attention):
+    """the streaming attention on the f16 matrix cores (ops.attention_fused_half; inference only): the reference side is prepared
+    once - by this pass (`key`: ops.attention_half_prepare, one launch) or by a session's frame 0 (`prepared`: what it kept) - and
+    every call is ONE launch for its one or two maps.  A later call for a map the first was not told of prepares and walks again."""
+    KEY, VALUE = 'half', 'half_val%d'
+
+    def __init__(self, b, n, hw, h, w, query=None, key=None, prepared=None):
+        _Attention.__init__(self, b, n, hw, h, w)
+        self.query, self.key, self.prepared = query, key, prepared
+
+    def attend(self, values, want_mass=True):
+        if torch.is_grad_enabled():
+            raise RuntimeError("half fused attention is an inference path: autograd is on")
+        prepared = self.prepared if want_mass else None
+        if prepared is None:
+            prepared = ops.attention_half_prepare(self.key, values, self.n)
+        outs, mass = ops.attention_fused_half(self.query, prepared, want_mass=want_mass)
+        if want_mass:
+            self.mass = mass
+        self._offers(want_mass, prepared, prepared.vts)          # (the operand object: the planes and the first call's maps)
         return outs
 
 
@@ -1009,7 +1043,8 @@ class FewShotGenerator(nn.Module):
         attention-weighted sum of the N reference feature maps.  Both batched matrix products run on the gather-GEMM
         kernel as per-sample 1x1 convolutions over the h x w query positions, kept in the transposed arrangement
         attention_t[b, (n, p_key), y, x] so that the softmax is the channel softmax kernel.
-        The first call of a pass (attention None) chooses the kind that runs - streaming where its switch is set and the kernels serve
+        The first call of a pass (attention None) chooses the kind that runs - the half streaming kind in an inference pass where
+        attention_half_switch says so, streaming where its switch is set and the kernels serve
         the shape, query bands where attention_band_plan asks for them, else dense - and attends x together with a second feature map
         reference_encoding announced (self._atn_second: the label features under use_label_ref 'mul'; the dense kind leaves it to
         its own call).  The later call attention_module(xl, None, None, atn) picks that result up, or attends xl by what was kept."""
@@ -1024,12 +1059,15 @@ class FewShotGenerator(nn.Module):
         else:
             second = self.__dict__.get('_atn_second', None)
             cvs = [c] + ([second.shape[1]] if second is not None else [])
-            fused = attention_fused_switch(self) and ops.attention_fused_serves(b, n, hw, c, cvs)
-            grad = not fused and attention_fused_grad_switch() and ops.attention_fused_grad_serves(b, n, hw, c, cvs)
-            plan = None if fused or grad else attention_band_plan(b, n, hw, h, w)
+            half = attention_half_switch(self) and ops.attention_fused_half_serves(b, n, hw, c, cvs)
+            fused = not half and attention_fused_switch(self) and ops.attention_fused_serves(b, n, hw, c, cvs)
+            grad = not (half or fused) and attention_fused_grad_switch() and ops.attention_fused_grad_serves(b, n, hw, c, cvs)
+            plan = None if half or fused or grad else attention_band_plan(b, n, hw, h, w)
             key = self.attention_encode(label_ref, 'atn_key')            # [b*n, c, h, w]
             query = self.attention_encode(label, 'atn_query')            # [b, c, h, w]
-            if fused or grad:
+            if half:
+                atn = AttentionFusedHalf(b, n, hw, h, w, query, key)
+            elif fused or grad:
                 atn = AttentionFused(b, n, hw, h, w, query, key, grad)
             elif plan is not None:
                 atn = AttentionBands(plan, b, n, hw, h, w, query, _kmat(key, b, n, hw))
@@ -1049,7 +1087,8 @@ class FewShotGenerator(nn.Module):
         return outs[0], atn.handle(), atn.atn_vis()
 
     def attention_module_kept(self, kept, label):
-        """attention_module on the operands an infer.InferenceSession kept from frame 0 (`keep_references`): after a streaming frame 0
+        """attention_module on the operands an infer.InferenceSession kept from frame 0 (`keep_references`): after a half streaming
+        frame 0 kept.half, the prepared half operands; after a streaming frame 0
         kept.key / kept.vals, the key and reference features in their own NHWC memory; otherwise kept.kmat, the key encoding of the
         reference labels, and kept.xmats, the reference features that enter the attention (image encoder, then label encoder), each in
         the arrangement its GEMM reads - in query bands where the plan asks for them, the band buffer the session's own (static under a
@@ -1060,7 +1099,9 @@ class FewShotGenerator(nn.Module):
         n = self.n_shot
         b, (h, w) = query.shape[0], query.shape[2:]
         hw = h * w
-        if kept.key is not None:
+        if kept.half is not None:        # (the prepared operands of ops.attention_fused_half: no prep launch in a steady frame)
+            atn, values = AttentionFusedHalf(b, n, hw, h, w, query, prepared=kept.half), kept.half.vts
+        elif kept.key is not None:
             atn, values = AttentionFused(b, n, hw, h, w, query, kept.key), kept.vals
         else:
             plan, values = attention_band_plan(b, n, hw, h, w), kept.xmats

@@ -1160,6 +1160,93 @@ def attention_fused(query, key, values, n, want_mass=True, split=0):
                                    want_mass, False)[:2]
 
 
+class AttentionHalfOperands:
+    """the reference side of the half streaming attention as fsv_attention_half_prep leaves it: kh, kl [b, nps, c] (the high and the
+    low half plane of the keys), vts = [v_t [b, cv, nps] per value map] (half, key-contiguous), nps = n p rounded up to 32"""
+
+    def __init__(self, kh, kl, vts, b, n, p, c, cvs, nps):
+        self.kh, self.kl, self.vts = kh, kl, list(vts)
+        self.b, self.n, self.p, self.c, self.cvs, self.nps = b, n, p, c, list(cvs), nps
+
+    def tensors(self):
+        return [self.kh, self.kl] + self.vts
+
+
+def _attention_half_plan(b, n, p, c, cvs, want_mass, split):
+    """(nsplit, workspace floats, nps) of fsv_attention_fused_fwd_h for this shape, or None when the kernel does not serve it"""
+    out = (ctypes.c_longlong * 3)()
+    rc = lib.call_status("fsv_attention_fused_h_plan", b, n, p, c, cvs[0], cvs[1] if len(cvs) > 1 else 0, 1 if want_mass else 0,
+                         int(split), out)
+    plan = _attention_plan("fsv_attention_fused_h_plan", rc, out)
+    return None if plan is None else plan + (int(out[2]),)
+
+
+def attention_fused_half_serves(b, n, p, c, cvs):
+    """whether attention_fused_half serves these sizes (b samples, n references, p = h w positions, c key / query channels, cvs the
+    channel counts of the one or two value maps): every channel count a multiple of 8 up to 128 - the plan's answer"""
+    return 1 <= len(cvs) <= 2 and min(b, n, p, c) >= 1 and _attention_half_plan(b, n, p, c, list(cvs), True, 0) is not None
+
+
+def attention_half_prepare(key, values, n):
+    """the reference side of attention_fused_half, once per reference set (one launch, csrc/attention_h.hip): key [b n, c, h, w] and
+    one or two value maps [b n, cv, h, w], fp32 -> AttentionHalfOperands.  Forward only."""
+    ts = [key] + list(values)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise ValueError("attention_half_prepare is forward-only (an input requires grad)")
+    if not 1 <= len(values) <= 2 or any(t.dim() != 4 or t.dtype != torch.float32 for t in ts):
+        raise ValueError("attention_half_prepare: a key and one or two value maps, 4-D fp32, got %s"
+                         % [(tuple(t.shape), t.dtype) for t in ts])
+    bn, c, h, w = key.shape
+    if n < 1 or bn % n or any(tuple(v.shape[0:1] + v.shape[2:]) != (bn, h, w) for v in values):
+        raise ValueError("attention_half_prepare: key %s, values %s do not belong to %d references"
+                         % (tuple(key.shape), [tuple(v.shape) for v in values], n))
+    b, p, cvs = bn // n, h * w, [v.shape[1] for v in values]
+    plan = _attention_half_plan(b, n, p, c, cvs, True, 0)
+    if plan is None:
+        raise lib.FsvError("attention_half_prepare: channels %s are not served (multiples of 8 up to 128): ask "
+                           "attention_fused_half_serves" % ([c] + cvs))
+    nps = plan[2]
+    key = to_nhwc(key.detach())
+    values = [to_nhwc(v.detach()) for v in values]
+    kh, kl = [torch.empty((b, nps, c), dtype=torch.float16, device=key.device) for _ in range(2)]
+    vts = [torch.empty((b, cv, nps), dtype=torch.float16, device=key.device) for cv in cvs]
+    lib.check_device(key, kh, kl, *(values + vts))
+    v0, v1 = [lib.ptr(v) for v in values] + [None] * (2 - len(values))
+    v0t, v1t = [lib.ptr(v) for v in vts] + [None] * (2 - len(vts))
+    lib.call("fsv_attention_half_prep", lib.ptr(key), v0, v1, lib.ptr(kh), lib.ptr(kl), v0t, v1t, b, n, p, c, cvs[0],
+             cvs[1] if len(cvs) > 1 else 0, lib.stream_ptr())
+    return AttentionHalfOperands(kh, kl, vts, b, n, p, c, cvs, nps)
+
+
+def attention_fused_half(query, prepared, want_mass=True, split=0):
+    """attention_fused on the f16 matrix cores, for inference (csrc/attention_h.hip: split energies - about 22 bits -, plain half
+    probabilities and values, fp32 softmax and accumulation; the same bits on every run): query [b, c, h, w] fp32 as the query
+    encoder left it, prepared = attention_half_prepare(key, values, n) -> ([attended map [b, cv, h, w] per value map], mass
+    [b, h, w, n] or None), fp32.  Forward only.  split: as attention_fused."""
+    if torch.is_grad_enabled() and query.requires_grad:
+        raise ValueError("attention_fused_half is forward-only (an input requires grad)")
+    pr = prepared
+    if query.dim() != 4 or query.dtype != torch.float32 or tuple(query.shape[:2]) != (pr.b, pr.c) or \
+            query.shape[2] * query.shape[3] != pr.p:
+        raise ValueError("attention_fused_half: query %s %s does not belong to operands prepared for b = %d, c = %d, h w = %d"
+                         % (tuple(query.shape), query.dtype, pr.b, pr.c, pr.p))
+    b, c, h, w = query.shape
+    plan = _attention_half_plan(b, pr.n, pr.p, c, pr.cvs, want_mass, split)
+    if plan is None:
+        raise lib.FsvError("attention_fused_half: channels %s are not served (multiples of 8 up to 128)" % ([c] + pr.cvs))
+    nsplit, floats, _ = plan
+    query = to_nhwc(query.detach())
+    outs = [empty_nhwc(b, cv, h, w, query) for cv in pr.cvs]
+    mass = torch.empty((b, h, w, pr.n), dtype=torch.float32, device=query.device) if want_mass else None
+    ws = torch.empty(floats, dtype=torch.float32, device=query.device) if floats else None
+    lib.check_device(query, mass, ws, *(pr.tensors() + outs))
+    v0t, v1t = [lib.ptr(v) for v in pr.vts] + [None] * (2 - len(pr.vts))
+    o0, o1 = [lib.ptr(o) for o in outs] + [None] * (2 - len(outs))
+    lib.call("fsv_attention_fused_fwd_h", lib.ptr(query), lib.ptr(pr.kh), lib.ptr(pr.kl), v0t, v1t, o0, o1, lib.ptr(mass), b, pr.n,
+             pr.p, c, pr.cvs[0], pr.cvs[1] if len(pr.cvs) > 1 else 0, nsplit, lib.ptr(ws), floats, lib.stream_ptr())
+    return outs, mass
+
+
 class _AttentionFusedFn(torch.autograd.Function):
     """fsv_attention_fused_fwd_lse / fsv_attention_fused_bwd: saved are the operands, the outputs and one float per query"""
 

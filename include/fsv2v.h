@@ -581,6 +581,34 @@ int fsv_attention_fused_bwd(const float* q, const float* k, const float* v0, con
                             int B, int N, int P, int C, int C0, int C1, int nsplit, float* ws, long long ws_floats,
                             fsv_stream_t stream);
 int fsv_attention_fused_bwd_plan(int B, int N, int P, int C, int C0, int C1, int nsplit, long long* out);
+/* ---- the inference form on the f16 matrix cores (csrc/attention_h.hip): v_mfma_f32_32x32x16_f16, forward only, opt-in, no atomics,
+ * the same bits on every run whatever FSV_DETERMINISTIC says.  With h(x) = round-to-nearest-even to IEEE half:
+ *   split     for q and k: xh = h(x), xl = h((x - xh) * 2^11) (the remainder is exact in fp32; the scale keeps xl in half's normal
+ *             range whenever xh is)
+ *   energy    e = S_hh + 2^-11 * (S_hl + S_lh), S_hh = sum_c kh qh, S_hl + S_lh = sum_c (kh ql + kl qh): fp32 MFMA accumulations of
+ *             exact products, the cross terms in an accumulator tile of their own; the kl ql term is dropped (about 22 bits)
+ *   softmax   online, fp32 throughout: running maximum m, p = expf(e - m), l = sum p; the denominator and the masses from the
+ *             unrounded p
+ *   values    o = (sum_key h(p) h(v)) / l, accumulated in fp32 by the MFMA
+ *   order     keys ascending, key ranges combined by fsv_attention_fused_fwd's finishing launch in ascending order
+ *   range     operands must be finite and below 65504 in magnitude: a larger value becomes inf in h() and is the caller's error
+ * fsv_attention_half_prep, once per reference set (one launch): k fp32 [B][N P][C] -> the half planes kh, kl [B][NPs][C];
+ * v_i fp32 [B][N P][Ci] -> half v_it [B][Ci][NPs], key-contiguous (transposed through LDS tiles); NPs = N P rounded up to 32, the
+ * tail zero-filled; v1 nullable (v1t / C1 are not read then).
+ * fsv_attention_fused_fwd_h: q fp32 [B][P][C] as the query encoder left it (split in registers, once per workgroup), the prepared
+ * operands, o0 / o1 / mass fp32 laid out as fsv_attention_fused_fwd writes them; its nsplit rules, workspace formula, finishing
+ * launch, order of the checks and status codes (one launch when nsplit is 1 and mass is NULL, one more otherwise).
+ * fsv_attention_fused_h_plan: out[0] = nsplit, out[1] = the workspace in floats, out[2] = NPs; C1 = 0 for a single map.
+ * Contract: C, C0, C1 multiples of 8 and at most 128 (one instantiation: the production 128 / 128 / 128), N P < 2^31 - 64,
+ * B <= 65535: FSV_ERR_UNSUPPORTED beyond, nothing launched.  Null pointers (v1 / v1t / o1 / mass nullable as above), non-positive
+ * sizes: FSV_ERR_BAD_ARG, before anything else; then the contract; then nsplit above 8 or above the ceil(N P / 32) key tiles, or a
+ * workspace smaller than the formula: FSV_ERR_BAD_ARG. */
+int fsv_attention_half_prep(const float* k, const float* v0, const float* v1, void* kh, void* kl, void* v0t, void* v1t,
+                            int B, int N, int P, int C, int C0, int C1, fsv_stream_t stream);
+int fsv_attention_fused_fwd_h(const float* q, const void* kh, const void* kl, const void* v0t, const void* v1t, float* o0, float* o1,
+                              float* mass, int B, int N, int P, int C, int C0, int C1, int nsplit, float* ws, long long ws_floats,
+                              fsv_stream_t stream);
+int fsv_attention_fused_h_plan(int B, int N, int P, int C, int C0, int C1, int want_mass, int nsplit, long long* out);
 /* state = {t, 1-beta1^t, 1-beta2^t, lr} on the device; gscale pre-multiplies the gradient (1/world_size) */
 int fsv_adam_step(float* param, const float* grad, float* m, float* v, float* state, long long n, float beta1,
                   float beta2, float eps, float gscale, fsv_stream_t stream);
