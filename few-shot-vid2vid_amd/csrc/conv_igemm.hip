@@ -815,6 +815,41 @@ __global__ __launch_bounds__(256) void fsv_split_finish4_kernel(const float4* pa
   }
 }
 
+// finishing pass of the sub-pixel forward of conv3x3(nearest_x2(x)) (fsv_conv_up_subpixel_fwd): part = [class][split][N H W][C] dense
+// copies, one work-item per four channels of one OUTPUT pixel (2 y + ry, 2 x + rx) - its class is the pixel's parity, its row the
+// source pixel (y, x); out = act((sum_k part[class][k] * wscale + bias) * scale), k ascending; stores are consecutive 16-byte vectors
+__global__ __launch_bounds__(256) void fsv_up_subpixel_finish_kernel(const float4* part, int nsplit, float4* out, const float* bias,
+                                                                     const float* wscale, long long total4, int N, int H, int W,
+                                                                     int C4, int act, float scale) {
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long stride = (long long)gridDim.x * 256;
+  const long long mc = (long long)N * H * W;
+  const float ws = wscale ? wscale[0] : 1.f;
+  for (; i < total4; i += stride) {
+    const int c4 = (int)(i % C4);
+    const long long pix = i / C4;
+    const int ox = (int)(pix % (2 * W));
+    const long long t = pix / (2 * W);
+    const int oy = (int)(t % (2 * H)), n = (int)(t / (2 * H));
+    const int cls = (oy & 1) * 2 + (ox & 1);
+    const long long m = ((long long)n * H + (oy >> 1)) * W + (ox >> 1);
+    const float4* src = part + ((long long)cls * nsplit * mc + m) * C4 + c4;
+    float4 v = src[0];
+#pragma unroll 4
+    for (int k = 1; k < nsplit; ++k) {
+      const float4 u = src[(long long)k * mc * C4];
+      v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+    }
+    v.x *= ws; v.y *= ws; v.z *= ws; v.w *= ws;
+    if (bias) {
+      const float* b = bias + 4 * c4;
+      v.x += b[0]; v.y += b[1]; v.z += b[2]; v.w += b[3];
+    }
+    v.x = fsv_act(v.x * scale, act); v.y = fsv_act(v.y * scale, act); v.z = fsv_act(v.z * scale, act); v.w = fsv_act(v.w * scale, act);
+    out[i] = v;
+  }
+}
+
 // the finishing pass that ALSO leaves the per-channel (sum, sum of squares) of the finished output for the normalisation that
 // follows (second session of round 6).  A K-split launch had no statistics epilogue - the splits only hold partial outputs - so its
 // consumer ran a reduction pass of its own (fsv_red2_kernel<0>: 60 launches of 5 - 6 us per step, one in every conv -> norm chain of
@@ -2297,6 +2332,107 @@ int fsv_conv_group_plan(const int* Mz, const int* Cout, const int* nchunks, cons
   for (int i = 0; i < n; ++i) { ps[i].Mz = Mz[i]; ps[i].Cout = Cout[i]; ps[i].nchunks = nchunks[i]; }
   *tile_out = fsv_group_tile(ps, nsamp, n);
   return FSV_OK;
+}
+
+// ---- conv3x3(nearest_x2(x)) forward of the DEEP layers: the four parity classes as one grid, K split in order -----------------
+// (include/fsv2v.h: fsv_conv_up_subpixel_fwd.)  One tile shape and one split factor for the four class problems together: they
+// are four equal GEMMs of M = N H W pixels and K = 4 Cin, so fsv_conv_cost sees them as one launch of 4 M pixels.
+static int fsv_up_subpixel_plan(int N, int H, int W, int Cin, int Cout, int force_tile, int force_split, int* tile_out,
+                                int* nsplit_out) {
+  const long long mc = (long long)N * H * W;
+  if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return FSV_ERR_BAD_ARG;
+  if ((4 * Cin) % FSV_BK != 0 || (Cout & 3) != 0 || 4 * mc * Cout > 0x7fffffffll) return FSV_ERR_UNSUPPORTED;
+  const int nchunks = 4 * Cin / FSV_BK;
+  int only = -1;
+  if (force_tile >= 0) {                 // like the grouped launch: a forced id counts for its shape
+    const FsvTile* row = fsv_tile_row(force_tile);
+    if (!row) return FSV_ERR_BAD_ARG;
+    only = row->shape;
+  }
+  static const int splits[6] = {1, 2, 3, 4, 6, 8};
+  double best = 1e30;
+  int bt = -1, bs = 1;
+  fsv_plan_candidates(Cout, only, [&](int t, double weight) {
+    for (int si = 0; si < 6; ++si) {
+      const int use = force_split > 0 ? force_split : splits[si];
+      if (force_split <= 0 && use > 1 && nchunks / use < 8) break;
+      const double c = fsv_conv_cost((int)(4 * mc), Cout, nchunks, 1, t, use) * weight;
+      if (c < best) { best = c; bt = t; bs = use; }
+      if (force_split > 0) break;
+    }
+  });
+  if (bt < 0) { bt = only >= 0 ? only : 4; bs = force_split > 0 ? force_split : 1; }
+  if (bs > nchunks) bs = nchunks;
+  *tile_out = bt; *nsplit_out = bs;
+  return FSV_OK;
+}
+
+int fsv_conv_up_subpixel_plan(int N, int H, int W, int Cin, int Cout, int force_tile, int force_split, int* tile_out,
+                              int* nsplit_out, long long* workspace_floats) {
+  if (!tile_out || !nsplit_out || !workspace_floats) return FSV_ERR_BAD_ARG;
+  if (const int bad = fsv_up_subpixel_plan(N, H, W, Cin, Cout, force_tile, force_split, tile_out, nsplit_out)) return bad;
+  *workspace_floats = *nsplit_out > 1 ? 4ll * *nsplit_out * N * H * W * Cout : 0ll;
+  return FSV_OK;
+}
+
+int fsv_conv_up_subpixel_fwd(const float* x, const float* wt, int ldw, const float* bias, const float* res, const float* wscale,
+                             int act, float scale, float* out, double* stats, int N, int H, int W, int Cin, int Cout,
+                             int per_sample, float* workspace, long long workspace_floats, int force_tile, int force_split,
+                             hipStream_t stream) {
+  if (!x || !wt || !out) return FSV_ERR_BAD_ARG;
+  if (res || stats || per_sample || act == FSV_ACT_DLRELU) return FSV_ERR_UNSUPPORTED;
+  int tile = 0, nsplit = 1;
+  if (const int bad = fsv_up_subpixel_plan(N, H, W, Cin, Cout, force_tile, force_split, &tile, &nsplit)) return bad;
+  const long long mc = (long long)N * H * W;
+  if (nsplit > 1) {
+    if (!workspace || workspace_floats < 4ll * nsplit * mc * Cout) return FSV_ERR_BAD_ARG;
+    if ((((unsigned long long)workspace | (unsigned long long)out) & 15ull) != 0) return FSV_ERR_UNSUPPORTED;
+  }
+  ConvGroup g;
+  g.nprob = 4;
+  const FsvTile* row = fsv_tile_row(tile);
+  const int per = fsv_cdiv((int)mc, row->bm) * fsv_cdiv(Cout, row->bn) * nsplit;
+  for (int c = 0; c < FSV_GROUP_MAX; ++c) {
+    if (c >= 4) { g.p[c] = g.p[0]; g.tile_end[c] = 4 * per; continue; }
+    const int ry = c >> 1, rx = c & 1;
+    // class (ry, rx) reads x[s + r - 1 + i], i in {0, 1} per axis, and owns the output pixels (2 y + ry, 2 x + rx)
+    const int ty[4] = {ry - 1, ry - 1, ry, ry}, tx[4] = {rx - 1, rx, rx - 1, rx};
+    const float* wc = wt + (long long)c * 4 * Cin * ldw;
+    if (const int bad = fsv_conv_check_args(x, wc, out, N, H, W, Cin, Cout, 4, ty, tx, ldw)) return bad;
+    ConvP& p = g.p[c];
+    fsv_fill_convp(p, x, wc, bias, nullptr, out, wscale, N, H, W, Cin, H, W, Cout, 4, ty, tx, 1, 1, 2 * H, 2 * W, 2, 2, ry, rx, ldw,
+                   0, 0, 0, act, scale);
+    if (nsplit > 1) {
+      // every split stores a DENSE copy [M][Cout] of its class through the body's ordered-split store; 1 / sigma, the bias and the
+      // activation wait for the finishing pass, which also does the placement
+      p.nsplit = nsplit;
+      p.part = workspace + (long long)c * nsplit * mc * Cout;
+      p.part_stride = mc * Cout;
+      p.dense_out = 1;
+      p.wscale = nullptr;
+    }
+    g.tile_end[c] = (c + 1) * per;
+  }
+  const dim3 grid(4 * per);
+  int variant = -1;                      // the compiled-in default variant of the shape
+#define FSV_DEFAULT_OF(SHAPE, ID) if (tile == SHAPE) variant = ID;
+  FSV_CONV_SHAPE_DEFAULTS(FSV_DEFAULT_OF)
+#undef FSV_DEFAULT_OF
+  switch (variant) {
+#define FSV_GROUP_CASE(ID, SHAPE, BM, BN, WM, WN, PF, AF, MODE, DBG) \
+  case ID: FSV_LAUNCH((fsv_conv_igemm_group_kernel<BM, BN, WM, WN, PF, AF, MODE>), grid, dim3(64 * WM * WN), stream, g); break;
+    FSV_CONV_TILES(FSV_GROUP_CASE)
+#undef FSV_GROUP_CASE
+    default: return FSV_ERR_BAD_ARG;
+  }
+  if (nsplit > 1) {
+    const long long total4 = 4 * mc * (Cout / 4);
+    int g4 = (int)((total4 + 255) / 256);
+    if (g4 > 8192) g4 = 8192;
+    FSV_LAUNCH(fsv_up_subpixel_finish_kernel, dim3(g4), dim3(256), stream, (const float4*)workspace, nsplit, (float4*)out, bias,
+               wscale, total4, N, H, W, Cout / 4, act, scale);
+  }
+  return fsv_check_launch();
 }
 
 // Grouped weight gradients: every dwt is a ZEROED [Kpad][ldw] matrix (slices of the optimiser's per-pass arena); 64x64 tiles

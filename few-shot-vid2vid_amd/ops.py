@@ -484,6 +484,10 @@ class _ConvFn(torch.autograd.Function):
         if (y is None and fold and _up_subpixel_wanted(x.shape[0], x.shape[2], x.shape[3], cin, cout, geom, per_sample, res) and
                 (not st_wanted or _os.environ.get('FSV_UP_SUBPIXEL_STATS', '1') == '1')):
             y = _up_subpixel_forward(x, w4_sub, cout, b, act, scale, inv_sub, cached=up_cached, keep=frozen)
+        # the deep layers (fewer source pixels, Cin >= 512): the same arithmetic as one grouped, K-split launch of the four classes
+        if (y is None and fold and
+                _up_subpixel_deep_wanted(x.shape[0], x.shape[2], x.shape[3], cin, cout, geom, per_sample, res, st_wanted)):
+            y = _up_subpixel_deep_forward(x, w4_sub, cout, b, act, scale, inv_sub, cached=up_cached, keep=frozen)
         if y is None:
             y = conv_forward(x, wt, ldw, cout, geom, bias=b, res=res.detach() if res is not None else None, act=act,
                              scale=scale, per_sample=per_sample, wscale=wscale, stats=st, up=fold)
@@ -614,7 +618,8 @@ class _ConvFn(torch.autograd.Function):
 # output parity class: 16 instead of 36 taps per source pixel.  As ONE grouped launch of four placed problems it measured slower than
 # the single gather through the up-sampling index (46.42 against 45.84 ms per step: the grouped kernel's rate on short-K placed
 # problems) and was removed; as four PLAIN launches on the layers large enough not to K-split it wins 0.65 ms: _up_subpixel_forward
-# below; profiles/r05_notes.md sections 10 - 11.)
+# below; profiles/r05_notes.md sections 10 - 11.  The deep layers - long K, too few pixels for a class to fill the chip - take the
+# grouped form WITH an ordered K split and a placed finishing pass: _up_subpixel_deep_forward, -0.49 ms, profiles/up_deep_notes.md.)
 class _TapGeom:
     """the part of conv.Geom the raw weight-gradient launch reads, for an explicit tap list"""
 
@@ -739,6 +744,63 @@ def _up_subpixel_forward(x, w4, cout, bias, act, scale, wscale, cached=None, kee
             wt, _, ldw = prep_weight(v, 0, Geom(3, 3, 1, 1), khs[4 * c:4 * c + 4], kws[4 * c:4 * c + 4], None)
         _conv.gather_gemm(x, wt, ldw, cout, h, w, ty, tx, 1, 1, bias=bias, act=act, scale=scale, out=y,
                           place=(2 * h, 2 * w, 2, 2, ry, rx), force_split=1, wscale=wscale)
+    return y
+
+
+_UP_DEEP_MIN_CIN = 512
+
+
+def _up_subpixel_deep_wanted(n, h, w, cin, cout, geom, per_sample, res, st_wanted):
+    """the DEEP layers of conv3x3(nearest_x2(x)) - fewer source pixels than _up_subpixel_wanted asks for, where a class of its own
+    cannot fill the chip - take the same 16-product arithmetic as ONE grouped launch of the four classes with an ordered K split
+    (csrc/conv_igemm.hip fsv_conv_up_subpixel_fwd).  A function of the shape alone.  Cin >= 512: the class problems then have
+    K >= 2048 - on short K the grouped kernel loses to the single gather (profiles/r05_notes.md section 10)."""
+    return (_os.environ.get('FSV_UP_SUBPIXEL', '1') == '1' and not per_sample and res is None and not st_wanted and geom.kh == 3 and
+            geom.kw == 3 and geom.stride == 1 and geom.pad == 1 and cin >= _UP_DEEP_MIN_CIN and (4 * cin) % 32 == 0 and cout % 4 == 0 and
+            not _up_subpixel_wanted(n, h, w, cin, cout, geom, per_sample, res))
+
+
+def up_subpixel_plan(n, h, w, cin, cout, force_tile=-1, force_split=0):
+    """(tile id, split-K factor, workspace floats) of fsv_conv_up_subpixel_fwd for this layer; None for a layer outside its contract"""
+    tile, nsplit, ws = ctypes.c_int(0), ctypes.c_int(1), ctypes.c_longlong(0)
+    rc = lib.call_status("fsv_conv_up_subpixel_plan", n, h, w, cin, cout, force_tile, force_split, ctypes.byref(tile),
+                         ctypes.byref(nsplit), ctypes.byref(ws))
+    if rc == lib.ENUMS['FSV_ERR_UNSUPPORTED']:
+        return None
+    if rc != 0:
+        raise lib.FsvError("fsv_conv_up_subpixel_plan failed with fsv_status %d" % rc)
+    return tile.value, nsplit.value, ws.value
+
+
+def _up_subpixel_deep_forward(x, w4, cout, bias, act, scale, wscale, cached=None, keep=None, force_tile=-1, force_split=0):
+    """_up_subpixel_forward's arithmetic for the deep layers: one entry, one grouped launch of the four placed class problems and -
+    when the plan splits K - one finishing pass that sums the splits in order and places the result.  Returns None when the library
+    declines (the caller takes the single gather)."""
+    n, cin, h, w = x.shape
+    plan = up_subpixel_plan(n, h, w, cin, cout, force_tile, force_split)
+    if plan is None:
+        return None
+    if cached is not None:
+        wall, ldw = cached
+    else:
+        v = _tap_sums(w4, _SUBPIXEL_ROWS)
+        cls = [(ry, rx) for ry in (0, 1) for rx in (0, 1)]
+        khs = [2 * ry + iy for ry, rx in cls for iy in (0, 1) for _ in (0, 1)]
+        kws = [2 * rx + ix for ry, rx in cls for _ in (0, 1) for ix in (0, 1)]
+        wall, _, ldw = prep_weight(v, 0, Geom(3, 3, 1, 1), khs, kws, None)
+        if keep is not None and keep.can_grow():
+            keep.up_fwd = (wall, ldw)
+    y = empty_nhwc(n, cout, 2 * h, 2 * w, x)
+    need = plan[2]
+    ws = torch.empty(need, dtype=torch.float32, device=x.device) if need else None
+    lib.check_device(x, wall, bias, y, wscale, ws)
+    rc = lib.call_status("fsv_conv_up_subpixel_fwd", lib.ptr(x), lib.ptr(wall), ldw, lib.ptr(bias), None, lib.ptr(wscale), act,
+                         float(scale), lib.ptr(y), None, n, h, w, cin, cout, 0, lib.ptr(ws), need, force_tile, force_split,
+                         lib.stream_ptr())
+    if rc == lib.ENUMS['FSV_ERR_UNSUPPORTED']:
+        return None
+    if rc != 0:
+        raise lib.FsvError("fsv_conv_up_subpixel_fwd failed with fsv_status %d" % rc)
     return y
 
 

@@ -92,6 +92,25 @@ typedef struct fsv_conv_desc {
 int fsv_conv_gather_group(const fsv_conv_desc* problems, int n, int force_tile, fsv_stream_t stream);
 /* tile id the grouped launch uses for problems of these sizes (Mz = pixels per sample group, nchunks = ceil(taps * Cin / 32)) */
 int fsv_conv_group_plan(const int* Mz, const int* Cout, const int* nchunks, const int* nsamp, int n, int* tile_out);
+/* ---- conv3x3(nearest_x2(x)) forward of the deep layers as its four sub-pixel classes (generator.py:489-493, 559-563) ----------
+ * out[n, 2y + ry, 2x + rx, :] = act((sum_{iy, ix in {0, 1}} x[n, y + ry - 1 + iy, x + rx - 1 + ix, :] @ wt[class (ry, rx)][tap (iy, ix)]
+ *                                     * wscale + bias) * scale): 16 products per source pixel and channel pair instead of the 36 of the
+ * gather through the up-sampling index.  x: NHWC fp32 [N][H][W][Cin] at SOURCE resolution; out: [N][2H][2W][Cout]; wt: the
+ * class-major 16-tap K-major layout [16 Cin][ldw] (class c = 2 ry + rx owns rows [4 c Cin, 4 (c + 1) Cin), taps (iy, ix) row-major,
+ * summed weights W0 | W1 + W2 resp. W0 + W1 | W2 per axis).  The four class problems run as ONE grouped launch with one tile shape
+ * and one K-split factor, planned for the four together (fsv_conv_up_subpixel_plan; force_tile / force_split as in
+ * fsv_conv_gather_fwd, a tile id counts for its shape).  nsplit > 1: split k of class c stores a dense copy into
+ * workspace[c][k][N H W][Cout] and ONE finishing launch sums the copies in ascending k, applies wscale, bias, activation and scale
+ * and stores to the placed positions - no atomics, the same bits on every run; workspace (16-byte aligned) must then hold
+ * the plan's workspace_floats: FSV_ERR_BAD_ARG otherwise.  nsplit == 1 ignores the workspace.  Allocates nothing, keeps nothing.
+ * Contract: (4 Cin) % 32 == 0, Cout % 4 == 0, fewer than 2^31 output elements, and no residual, statistics or per-sample weights -
+ * res, stats non-null or per_sample != 0: FSV_ERR_UNSUPPORTED, nothing launched (the caller takes the single gather, in_up = 1). */
+int fsv_conv_up_subpixel_plan(int N, int H, int W, int Cin, int Cout, int force_tile, int force_split, int* tile_out,
+                              int* nsplit_out, long long* workspace_floats);
+int fsv_conv_up_subpixel_fwd(const float* x, const float* wt, int ldw, const float* bias, const float* res, const float* wscale,
+                             int act, float scale, float* out, double* stats, int N, int H, int W, int Cin, int Cout,
+                             int per_sample, float* workspace, long long workspace_floats, int force_tile, int force_split,
+                             fsv_stream_t stream);
 /* grouped weight gradients (arguments of fsv_conv_wgrad): every dwt is a ZEROED [Kpad][ldw] matrix; float4-gather layers only
  * (Cin % 4 == 0), FSV_ERR_UNSUPPORTED with nothing launched otherwise - issue the problems one by one then */
 typedef struct fsv_wgrad_desc {
