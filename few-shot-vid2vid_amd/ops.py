@@ -2872,3 +2872,36 @@ def pool_rows(x, oh=32, ow=32):
     if x.dtype != torch.float32:
         raise NotImplementedError("pool_rows: fp32 feature maps only (got %s)" % x.dtype)
     return _PoolRowsFn.apply(x, int(oh), int(ow))
+
+
+def roll_flip(ref_stacks, params):
+    """The adaptation target of test-time finetuning (model.Vid2VidModel.finetune) from the reference stacks, one launch for all of
+    them (csrc/roll_flip.hip): for every t [B, N, C, H, W] of `ref_stacks` (one or two fp32 tensors with the same B, N, H, W - label
+    and image) the dense NCHW tensor [B, C, H, W]
+
+        torch.flip(roll_w(roll_h(t[:, idx], ny), nx), [3]) if flip else roll_w(roll_h(t[:, idx], ny), nx)
+
+    bit for bit, where roll_h(t, ny) = cat([t[:, :, -ny:], t[:, :, :-ny]], 2) and roll_w likewise along W.  `params` is a DEVICE
+    int32[4] = (idx, ny, nx, flip) that the kernel reads: a captured launch gives a new target after the four integers were
+    overwritten.  The kernel clamps idx into [0, N), reduces ny / nx modulo H / W and reads flip as != 0; whoever writes `params`
+    validates what it writes.  Forward only: inputs that require grad are refused."""
+    stacks = list(ref_stacks)
+    if not 1 <= len(stacks) <= 2:
+        raise ValueError("roll_flip takes one or two reference stacks (got %d)" % len(stacks))
+    for t in stacks:
+        if t.dim() != 5 or t.dtype != torch.float32:
+            raise ValueError("roll_flip: [B, N, C, H, W] fp32 stacks expected (got %s %s)" % (tuple(t.shape), t.dtype))
+        if t.requires_grad:
+            raise ValueError("roll_flip is forward-only: an input requires grad")
+    b, n, _, h, w = stacks[0].shape
+    if any((t.shape[0], t.shape[1], t.shape[3], t.shape[4]) != (b, n, h, w) for t in stacks):
+        raise ValueError("roll_flip: the stacks differ in B, N, H or W: %s" % [tuple(t.shape) for t in stacks])
+    if params.dtype != torch.int32 or params.numel() != 4 or not params.is_contiguous() or params.device != stacks[0].device:
+        raise ValueError("roll_flip: params is a contiguous int32[4] on the stacks' device")
+    stacks = [t if t.is_contiguous() else t.contiguous() for t in stacks]
+    outs = [torch.empty((b, t.shape[2], h, w), dtype=torch.float32, device=t.device) for t in stacks]
+    lib.check_device(params, *stacks)
+    second = len(stacks) == 2
+    lib.call("fsv_roll_flip", lib.ptr(stacks[0]), lib.ptr(outs[0]), stacks[0].shape[2], lib.ptr(stacks[1]) if second else None,
+             lib.ptr(outs[1]) if second else None, stacks[1].shape[2] if second else 0, b, n, h, w, lib.ptr(params), lib.stream_ptr())
+    return outs

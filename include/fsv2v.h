@@ -534,6 +534,17 @@ int fsv_adaptive_avgpool_bwd(const float* dy, float* dx, int N, int H, int W, in
  * OW <= 40) */
 int fsv_pool_rows_fwd(const float* x, float* rows, int N, int H, int W, int C, int OH, int OW, fsv_stream_t stream);
 int fsv_pool_rows_bwd(const float* drows, float* dx, int N, int H, int W, int C, int OH, int OW, fsv_stream_t stream);
+/* csrc/roll_flip.hip - the adaptation target of test-time finetuning (vid2vid_model.py:207-237, util/util.py:157-168) for up to two
+ * tensors (label and image) in one launch:
+ *     dst[b][c][y][x] = src[b][idx][c][(y - ny) mod H][(x' - nx) mod W],   x' = flip ? W - 1 - x : x
+ * src_t dense fp32 [B][N][C_t][H][W], dst_t dense NCHW fp32 [B][C_t][H][W]; src1 / dst1 are not read when C1 = 0.  params is a DEVICE
+ * int32[4] = {idx, ny, nx, flip} read by the kernel (a captured launch follows the buffer): idx is clamped into [0, N), ny / nx are
+ * reduced modulo H / W (negative values included), flip is read as != 0 - no value of the four integers takes an index outside the
+ * tensors.  Pure data movement, bit-exact.  Null src0 / dst0 / params (src1 / dst1 with C1 > 0), non-positive B / N / H / W / C0,
+ * negative C1: FSV_ERR_BAD_ARG; more than 2^31 - 1 workgroups (B (C0 + C1) H ceil(W / 256)): FSV_ERR_UNSUPPORTED; nothing is launched
+ * in either case. */
+int fsv_roll_flip(const float* src0, float* dst0, int C0, const float* src1, float* dst1, int C1, int B, int N, int H, int W,
+                  const int* params, fsv_stream_t stream);
 /* softmax over the contiguous channel dimension of [rows][C] (nn.Softmax(dim=1) at generator.py:384).  gsum != NULL: the launch
  * also writes gsum[rows][groups], gsum[row][g] = the sum of y[row][j] over the g-th contiguous slice of C / groups channels (the
  * attention mass per reference, generator.py:310,366), accumulated in fp32 in a fixed order, no atomics; y has the same bits with
